@@ -1,7 +1,7 @@
 """Headline benchmark (BASELINE.json): output voxels/s of 3-D sliding-window segmentation --
 512^3 fp32 synthetic CT volume, 96^3 windows, overlap 0.5 (1000 windows), 5-class BasicUNet, gaussian blend.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,11 @@ all 1000 windows, (N > 1: RCCL all-gather of the per-window logits,) blend + nor
 ``create_test_image_3d`` phantom of SURVEY.md 8(d) config 1, restated bit-identically in oracle/synthetic.py -- is resident
 in HBM before the timed region.  N > 1 shards the windows of the SAME volume over the ranks (strong scaling, config 2 of
 BASELINE.json).  Rank 0 prints ONE JSON line of numbers and short labels (< 6 KB: the driver keeps a bounded tail of stdout); what every
-key means, how it is measured and which caveats apply is written down ONCE in DESIGN.md section 7 ("the bench line"), not in the line:
+key means, how it is measured and which caveats apply is written down ONCE in DESIGN.md section 7 ("the bench line"), not in the line.
+
+A plain run sets up, warms up, times the K steps (no per-launch events in the timed region), writes --dump-outputs and prints the
+headline keys (metric, value, unit, ms_per_step, dtype, ... and checksum = the sum of the last step's logits).  --full adds the
+per-kernel spans in the timed region and everything below, which takes minutes of its own:
 
   parity              the headline family's whole-volume parity against the CPU oracle (134 217 728 voxels x 5 logits), at top level
   reference_self_spread   the oracle against ITSELF (1 thread vs the pool's thread layout; oneDNN off vs on): what "bit-exact argmax" means for the reference
@@ -355,21 +359,46 @@ def build_net(name: str, roi: int, dev, features=None):
     return net.eval().to(dev)
 
 
-def timed_steps(inferer, vol, net, steps: int, warmup: int, sync):
-    """W untimed warm-up steps, then exactly K steps bracketed by barrier + device synchronise on both sides"""
+def timed_steps(inferer, vol, net, steps: int, warmup: int, sync, profile: bool = True):
+    """W untimed warm-up steps, then exactly K steps bracketed by barrier + device synchronise on both sides; profile=True records
+    per-launch HIP events of the dominant kernels inside the timed region (the spans the rooflines are priced from), False leaves them out"""
     from monai_amd import _prof
 
     out = None
     for _ in range(warmup):
         out = inferer(vol, net)
     sync()
-    _prof.start()
+    if profile:
+        _prof.start()
     t0 = time.perf_counter()
     for _ in range(steps):
         out = inferer(vol, net)
     sync()
     dt = time.perf_counter() - t0
-    return dt, _prof.stop(), out
+    return dt, (_prof.stop() if profile else {}), out
+
+
+DUMP_SAMPLE = 1 << 22      # logits drawn at seeded positions for --dump-outputs: 16 MB of float32
+
+
+def dump_outputs(out: torch.Tensor, path: str) -> None:
+    """what the timed path returned in its last step, as .npy files under `path` (about 21 MB at 512^3): `logits_sample` (float32 at DUMP_SAMPLE positions drawn
+    with a fixed seed from the flat [1, C, D, H, W] logits, sorted; every value when there are fewer), `logits_center_plane` (float32 [C, H, W] at depth D // 2)
+    and `logits_class_sums` (float64 [C], each class summed over the whole volume) -- the same positions for the same --size, so two builds compare output for output"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    flat = out.reshape(-1)
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        sample = flat
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+        sample = flat[torch.from_numpy(idx).to(flat.device)]
+    arrays = {"logits_sample": sample.float(), "logits_center_plane": out[0, :, out.shape[2] // 2].float(),
+              "logits_class_sums": out[0].sum(dim=(1, 2, 3), dtype=torch.float64)}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def _traffic(roof: dict, key: str) -> None:
@@ -750,17 +779,27 @@ def _fit_line(line, limit: int = LINE_BYTES_MAX):
     return line
 
 
+def _progress(what: str) -> None:
+    """--full: one stderr line before each leg that takes minutes (stdout keeps the single JSON line)"""
+    print(f"bench --full: {what}", file=sys.stderr, flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-kernel spans in the timed region and the rooflines priced from them, the in-run "
+                                                        "counter passes, the CPU baseline with its parity check and reference_self_spread, the per-rank breakdown and "
+                                                        "the extras; without it the run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step returned as DIR/*.npy (bench.dump_outputs)")
     ap.add_argument("--size", type=int, default=512, help="volume edge (512 = the BASELINE.json workload)")
     ap.add_argument("--roi", type=int, default=96)
     ap.add_argument("--cpu-windows", type=int, default=1000, help="windows the CPU baseline / parity check runs: >= the volume's window count (1000) = the WHOLE volume, "
                                                                   "fewer = a corner sub-volume (125 = 288^3), 0 = skip")
-    ap.add_argument("--cpu-budget-s", type=float, default=float(os.environ.get("MONAI_AMD_BENCH_CPU_BUDGET_S", "900")),
-                    help="seconds the CPU leg may take; a probe batch prices it and the largest corner sub-volume that fits is taken when the whole volume would not")
+    ap.add_argument("--cpu-budget-s", type=float, default=float(os.environ.get("MONAI_AMD_BENCH_CPU_BUDGET_S", "300")),
+                    help="seconds the CPU leg may take; a probe batch prices it and the largest corner sub-volume that fits is taken when the whole volume would not "
+                         "(300: the whole volume on a 16-CPU share, about 180 s, and a --full run inside 10 minutes)")
     ap.add_argument("--no-spread", action="store_true", help="skip reference_self_spread (the oracle against itself under other thread layouts / without oneDNN)")
     ap.add_argument("--spread-budget-s", type=float, default=90.0, help="seconds the reference_self_spread leg may take (it sizes its corner sub-volumes by it)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the in-run hardware-counter passes behind roofline*.traffic (two rocprofv3 child processes, ~1 min)")
@@ -774,6 +813,8 @@ def main(argv=None):
                                                                "probe, one async all_gather_into_tensor per round) -- the N > 1 path exercised on a one-GPU box; the line is a development record "
                                                                "(`forced_shard`), not the headline")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -828,22 +869,19 @@ def main(argv=None):
         if not emulated:
             torch.cuda.synchronize()
 
-    dt, spans, out = timed_steps(inferer, vol, net, args.steps, args.warmup, sync)
+    dt, spans, out = timed_steps(inferer, vol, net, args.steps, args.warmup, sync, profile=args.full)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    ranks = per_rank_breakdown(spans, args.steps, world, dev, dist) if (world > 1 or forced) else None
+    ranks = per_rank_breakdown(spans, args.steps, world, dev, dist) if args.full and (world > 1 or forced) else None
 
     if rank == 0:
         voxels = float(args.size) ** 3
         ms = 1e3 * dt / args.steps
-        profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")      # no profiler inside a profiler
-        if world == 1 and not forced and not emulated and not args.no_pmc and not profiled and args.net == "basicunet" and (args.size, args.roi) == (512, 96):
-            _PMC_INRUN.update(pmc_inrun())
+        if args.dump_outputs:
+            dump_outputs(out, args.dump_outputs)
         exact = config.conv_algo() in (config.CONV_ALGOS["fp32"], config.CONV_ALGOS["direct"], config.CONV_ALGOS["wino2d"])
-        conv_all = {k.split("/")[1]: {"ms": round(v["ms_total"] / args.steps, 3), "tflops": round(v["work"] / (v["ms_total"] * 1e-3) / 1e12, 2)}
-                    for k, v in spans.items() if k.startswith("conv3d_k3/")}
         family = "fp32-exact" if exact else "split-fp16"
         line = {
             "metric": METRIC,
@@ -857,68 +895,79 @@ def main(argv=None):
             "scaling": "strong",
             "vs_baseline": None,
             "dtype": "f32",
-            "dtype_note": "fp32 tensors + accumulators; conv products " + ("exact fp32" if exact else "from hi+lo fp16 pieces (fp32-equivalent); extra.fp32_exact = exact kernels"),
+            "dtype_note": "fp32 tensors + accumulators; conv products " + ("exact fp32" if exact else "from hi+lo fp16 pieces (fp32-equivalent); --full: extra.fp32_exact = exact kernels"),
             "data": "synthetic",
             "config": {
                 "workload": f"{NETS[args.net]} 5-class seed 1, {args.size}^3 CT phantom in HBM, {args.roi}^3 win ov 0.5 gaussian, sw_batch 4 (engine: <= 64 windows per launch)",
                 "parallelism": ("1 GPU, sharded code forced on a one-rank RCCL group" if forced else "1 GPU") if world == 1 else f"windows sharded over {world} GPUs, RCCL all-gather of logits before the blend",
             },
-            "parity": None,
-            "roofline": conv_roofline(spans, args.steps, ms, args.roi),
-            "roofline_hbm": blend_roofline(spans, mosaic=world == 1 and not forced and hasattr(net, "forward_into_windows") and os.environ.get("MONAI_AMD_LOGITS_LAYOUT") != "windows"),
-            "conv_ms_per_step": conv_all,
-            "upconv": ({"kernel": "upconv_k4s2_h2_kernel (UpCat: convT k4 s2 of the low-res tensor)", "ms_per_step": spans["upconv_k4s2"]["ms_total"] / args.steps,
-                        "ms_avg": spans["upconv_k4s2"]["ms_avg"], "fp32_equivalent_tflops": spans["upconv_k4s2"]["work"] / (spans["upconv_k4s2"]["ms_total"] * 1e-3) / 1e12}
-                       if "upconv_k4s2" in spans else None),
             "checksum": float(out.double().sum().item()),
-            "pmc": dict(_PMC_STATUS),
         }
-        if line["roofline_hbm"] is not None and not emulated:
-            cg = device_copy_gbps(dev)
-            line["roofline_hbm"]["device_copy_GBps"] = cg
-            line["roofline_hbm"]["frac_of_copy_ceiling"] = line["roofline_hbm"]["achieved"] / cg
-        if ranks is not None:
-            line["per_rank_ms_per_step"] = ranks
-            pred = max(r["predictor_ms"] for r in ranks)
-            line["exposed_comm_share"] = max(r["gather_wait_ms"] for r in ranks) / ms      # what the compute stream waited for gathers, of the step
-            line["predictor_ms_max"] = pred
         if forced:
             line["forced_shard"] = {"backend": dist.get_backend(), "inplace_gather_probe": [bool(v) for v in parallel.inplace_gather_verdicts().values()],
                                     "rounds": [n for _, n in parallel.partition(1000 if (args.size, args.roi) == (512, 96) else 1, 1, 0, force=True).schedule(64)][:12]}
         if emulated:
             line["emulated"] = "SIMT emulator + gloo: harness test only, not a measurement"
-        shared: dict = {}
-        if world == 1 and args.cpu_windows > 0 and args.net == "basicunet" and not forced:
-            spread_s = 0.0 if (emulated or args.no_spread) else args.spread_budget_s
-            try:
-                rec, par, spread = cpu_baseline(args.size, args.roi, args.cpu_windows, vol, net, inferer, out, args.cpu_budget_s, shared, spread_s)
-            except Exception as e:      # the checker's own failure (a dead pool worker, host memory) must not cost the headline line: fall back to one process on a 27-window corner
-                err = f"{type(e).__name__}: {e}"[:160]
+        if args.full:
+            profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")      # no profiler inside a profiler
+            if world == 1 and not forced and not emulated and not args.no_pmc and not profiled and args.net == "basicunet" and (args.size, args.roi) == (512, 96):
+                _progress("hardware-counter passes")
+                _PMC_INRUN.update(pmc_inrun())
+            conv_all = {k.split("/")[1]: {"ms": round(v["ms_total"] / args.steps, 3), "tflops": round(v["work"] / (v["ms_total"] * 1e-3) / 1e12, 2)}
+                        for k, v in spans.items() if k.startswith("conv3d_k3/")}
+            line.update({
+                "parity": None,
+                "roofline": conv_roofline(spans, args.steps, ms, args.roi),
+                "roofline_hbm": blend_roofline(spans, mosaic=world == 1 and not forced and hasattr(net, "forward_into_windows") and os.environ.get("MONAI_AMD_LOGITS_LAYOUT") != "windows"),
+                "conv_ms_per_step": conv_all,
+                "upconv": ({"kernel": "upconv_k4s2_h2_kernel (UpCat: convT k4 s2 of the low-res tensor)", "ms_per_step": spans["upconv_k4s2"]["ms_total"] / args.steps,
+                            "ms_avg": spans["upconv_k4s2"]["ms_avg"], "fp32_equivalent_tflops": spans["upconv_k4s2"]["work"] / (spans["upconv_k4s2"]["ms_total"] * 1e-3) / 1e12}
+                           if "upconv_k4s2" in spans else None),
+                "pmc": dict(_PMC_STATUS),
+            })
+            if line["roofline_hbm"] is not None and not emulated:
+                cg = device_copy_gbps(dev)
+                line["roofline_hbm"]["device_copy_GBps"] = cg
+                line["roofline_hbm"]["frac_of_copy_ceiling"] = line["roofline_hbm"]["achieved"] / cg
+            if ranks is not None:
+                line["per_rank_ms_per_step"] = ranks
+                pred = max(r["predictor_ms"] for r in ranks)
+                line["exposed_comm_share"] = max(r["gather_wait_ms"] for r in ranks) / ms      # what the compute stream waited for gathers, of the step
+                line["predictor_ms_max"] = pred
+            shared: dict = {}
+            if world == 1 and args.cpu_windows > 0 and args.net == "basicunet" and not forced:
+                spread_s = 0.0 if (emulated or args.no_spread) else args.spread_budget_s
+                _progress("CPU-oracle baseline and parity")
                 try:
-                    os.environ["MONAI_AMD_BENCH_CPU_PROCS"] = "1"
-                    rec, par, spread = cpu_baseline(args.size, args.roi, 27, vol, net, inferer, None, args.cpu_budget_s, shared, 0.0)
-                    rec["fallback_after"] = err
-                except Exception as e2:
-                    rec, par, spread = {"error": err, "fallback_error": f"{type(e2).__name__}: {e2}"[:160]}, None, None
-            if par is not None:
-                line["parity"] = _short_parity(par, family)
-                line["parity"]["compared"] = shared.get("what", "")
-                rec["parity_vs_gpu"] = {k: par[k] for k in ("ok", "mismatch_outside_margin", "max_abs_logit_diff", "voxels")}
-            line["cpu_baseline"] = rec
-            if spread is not None:
-                line["reference_self_spread"] = spread
-        else:
-            line["cpu_baseline"] = None
-        if world == 1 and args.net == "basicunet" and not args.no_extra and not emulated and not forced:
-            extra = {}
-            for name, fn in (("fp32_exact", lambda: extra_fp32_exact(args, vol, net, inferer, sync, shared)), ("direct_split", lambda: extra_direct_split(args, vol, net, inferer, sync)), ("config3", lambda: extra_config3(args, vol, sync, dev, shared)), ("unet", lambda: extra_unet(args, vol, sync, dev)),
-                             ("config4", lambda: extra_config4(dev))):
-                try:
-                    extra[name] = fn()
-                except Exception as e:      # an extra must never cost the headline line
-                    extra[name] = {"error": f"{type(e).__name__}: {e}"[:160]}
-                torch.cuda.empty_cache()
-            line["extra"] = _slim_extra(extra)
+                    rec, par, spread = cpu_baseline(args.size, args.roi, args.cpu_windows, vol, net, inferer, out, args.cpu_budget_s, shared, spread_s)
+                except Exception as e:      # the checker's own failure (a dead pool worker, host memory) must not cost the headline line: fall back to one process on a 27-window corner
+                    err = f"{type(e).__name__}: {e}"[:160]
+                    try:
+                        os.environ["MONAI_AMD_BENCH_CPU_PROCS"] = "1"
+                        rec, par, spread = cpu_baseline(args.size, args.roi, 27, vol, net, inferer, None, args.cpu_budget_s, shared, 0.0)
+                        rec["fallback_after"] = err
+                    except Exception as e2:
+                        rec, par, spread = {"error": err, "fallback_error": f"{type(e2).__name__}: {e2}"[:160]}, None, None
+                if par is not None:
+                    line["parity"] = _short_parity(par, family)
+                    line["parity"]["compared"] = shared.get("what", "")
+                    rec["parity_vs_gpu"] = {k: par[k] for k in ("ok", "mismatch_outside_margin", "max_abs_logit_diff", "voxels")}
+                line["cpu_baseline"] = rec
+                if spread is not None:
+                    line["reference_self_spread"] = spread
+            else:
+                line["cpu_baseline"] = None
+            if world == 1 and args.net == "basicunet" and not args.no_extra and not emulated and not forced:
+                extra = {}
+                for name, fn in (("fp32_exact", lambda: extra_fp32_exact(args, vol, net, inferer, sync, shared)), ("direct_split", lambda: extra_direct_split(args, vol, net, inferer, sync)), ("config3", lambda: extra_config3(args, vol, sync, dev, shared)), ("unet", lambda: extra_unet(args, vol, sync, dev)),
+                                 ("config4", lambda: extra_config4(dev))):
+                    _progress(f"extra.{name}")
+                    try:
+                        extra[name] = fn()
+                    except Exception as e:      # an extra must never cost the headline line
+                        extra[name] = {"error": f"{type(e).__name__}: {e}"[:160]}
+                    torch.cuda.empty_cache()
+                line["extra"] = _slim_extra(extra)
         line = _fit_line(_rounded(line))
         print(json.dumps(line))
     if world > 1 or forced:

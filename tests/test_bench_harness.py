@@ -1,17 +1,21 @@
 """bench.py's own code path without a GPU: the SIMT-emulator build of the kernels + gloo (MONAI_AMD_BENCH_EMULATOR=1), tiny sizes.
 Checks the wiring the driver relies on -- `python bench.py` and `python -m torch.distributed.run ... bench.py --gpus N` print exactly
-one JSON line on rank 0 with the contract's keys, the `roofline` / `roofline_hbm` / `cpu_baseline` objects, the enforced parity rule --
-and that sharding the windows over two ranks reproduces the single-process result bit for bit (same checksum).  Not a measurement."""
+one JSON line on rank 0 with the contract's keys, with --full the `roofline` / `roofline_hbm` / `cpu_baseline` objects and the enforced
+parity rule, without it the headline keys alone and the --dump-outputs files -- and that sharding the windows over two ranks reproduces
+the single-process result bit for bit (same checksum).  Not a measurement."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--size", "40", "--roi", "32", "--steps", "1", "--warmup", "0", "--harness-features", "8,8,16,16,32,8"]      # an eighth of the widths: the SIMT emulator pays for every flop
-KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
-        "roofline", "roofline_hbm", "cpu_baseline"}
+HEADLINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+                 "checksum"}
+KEYS = HEADLINE_KEYS | {"roofline", "roofline_hbm", "cpu_baseline"}
 
 
 def _run(cmd):
@@ -25,7 +29,7 @@ def _run(cmd):
 
 
 def test_bench_single_process_line():
-    line = _run([sys.executable, "bench.py", "--cpu-windows", "2"] + ARGS)
+    line = _run([sys.executable, "bench.py", "--full", "--cpu-windows", "2"] + ARGS)
     assert KEYS <= set(line) and line["n_gpus"] == 1 and line["unit"] == "voxels/s" and line["dtype"] == "f32" and line["emulated"]
     assert line["roofline"]["bound"] == "mfma" and 0.0 < line["roofline"]["frac"] and line["roofline"]["unit"] == "TFLOP/s"
     assert line["roofline_hbm"]["bound"] == "hbm" and line["roofline_hbm"]["peak"] == 8000.0
@@ -39,12 +43,47 @@ def test_bench_single_process_line():
     test_bench_single_process_line.checksum = line["checksum"]
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run: the headline keys and nothing that needs runs of its own; --dump-outputs writes the last step's logits (all of them at this size).
+    One 32^3 window: the line's wiring needs no more, and the emulator pays for every window"""
+    line = _run([sys.executable, "bench.py", "--dump-outputs", str(tmp_path), "--size", "32"] + ARGS[2:])
+    assert HEADLINE_KEYS <= set(line) and not set(line) & {"roofline", "roofline_hbm", "cpu_baseline", "parity", "extra", "pmc", "conv_ms_per_step"}
+    assert line["steps"] == 1 and line["warmup"] == 0 and line["ms_per_step"] > 0 and line["unit"] == "voxels/s" and line["higher_is_better"] is True
+    sample, plane, sums = (np.load(tmp_path / f"{n}.npy") for n in ("logits_sample", "logits_center_plane", "logits_class_sums"))
+    assert sample.dtype == np.float32 and sample.shape == (5 * 32 ** 3,) and plane.dtype == np.float32 and plane.shape == (5, 32, 32)
+    assert sums.dtype == np.float64 and sums.shape == (5,) and np.isfinite(sample).all()
+    assert abs(sample.astype(np.float64).sum() - line["checksum"]) <= 1e-9 * abs(line["checksum"]) and abs(sums.sum() - line["checksum"]) <= 1e-9 * abs(line["checksum"])
+
+
+def test_dump_outputs_sample_is_seeded_and_bounded(tmp_path, monkeypatch):
+    """bench.dump_outputs on an output larger than its sample: the same seeded positions every time, float32 / float64 only, and at 512^3 well under 64 MB"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import torch
+
+    assert 4 * bench.DUMP_SAMPLE + 4 * 5 * 512 * 512 + 8 * 5 < 64 << 20      # logits_sample + logits_center_plane + logits_class_sums of the benchmark's output
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1 << 12)      # a sample far smaller than the output, as at 512^3 (few repeated positions)
+
+    out = torch.arange(5 * 32 * 160 * 170, dtype=torch.float32).reshape(1, 5, 32, 160, 170)
+    for d in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["logits_center_plane.npy", "logits_class_sums.npy", "logits_sample.npy"]
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    sample = np.load(tmp_path / "a" / "logits_sample.npy")
+    assert 0.9 * bench.DUMP_SAMPLE < sample.size <= bench.DUMP_SAMPLE and np.all(np.diff(sample) > 0)      # sorted distinct positions of an arange
+    assert np.array_equal(np.load(tmp_path / "a" / "logits_center_plane.npy"), out[0, :, 16].numpy())
+    assert np.allclose(np.load(tmp_path / "a" / "logits_class_sums.npy"), out[0].double().sum(dim=(1, 2, 3)).numpy(), rtol=1e-12)
+
+
 def test_bench_two_ranks_line_and_bitwise_sharding():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     line = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                 "bench.py", "--gpus", "2"] + ARGS)
+                 "bench.py", "--gpus", "2", "--full"] + ARGS)
     assert KEYS <= set(line) and line["n_gpus"] == 2 and line["scaling"] == "strong" and line["cpu_baseline"] is None
     assert "sharded over 2" in line["config"]["parallelism"]
     single = getattr(test_bench_single_process_line, "checksum", None)
@@ -59,7 +98,7 @@ def test_bench_four_ranks_line_and_bitwise_sharding():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     line = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                 "bench.py", "--gpus", "4"] + ARGS)
+                 "bench.py", "--gpus", "4", "--full"] + ARGS)
     assert KEYS <= set(line) and line["n_gpus"] == 4 and line["scaling"] == "strong" and line["cpu_baseline"] is None
     assert "sharded over 4" in line["config"]["parallelism"] and [r["rank"] for r in line["per_rank_ms_per_step"]] == [0, 1, 2, 3]
     single = getattr(test_bench_single_process_line, "checksum", None)
