@@ -490,6 +490,27 @@ int mh_minmax_scale_f32(const float* src, float* dst, int C, int64_t n, const fl
  * read backwards when flip3[a] != 0 (HOST int32[3]).  Images with fewer spatial axes pass leading extents of 1. */
 int mh_flip_permute_f32(const float* src, float* dst, int C, const int32_t* in_size3, const int32_t* perm3, const int32_t* flip3, void* stream);
 
+/* ---- Segmentation metrics (DiceMetric / MeanIoU / ConfusionMatrixMetric) ------------------------------------- */
+
+#define MH_OV_CHANNEL 0 /* [B][K][n]: one stored value per class; float32 or uint8 (bool) */
+#define MH_OV_LABELS 1  /* [B][1][n]: class indices; float32 / int64 (truncated like .long()) or uint8 */
+#define MH_OV_F32 0
+#define MH_OV_U8 1
+#define MH_OV_I64 2
+/* One pass over a prediction and a ground truth in place of the per-class compare / masked_select / torch.sum loops of
+ * DiceHelper.__call__ + compute_channel (monai/metrics/meandice.py:281-337), compute_iou (monai/metrics/meaniou.py:130-147),
+ * get_confusion_matrix (monai/metrics/confusion_matrix.py:153-176) and is_binary_tensor (monai/metrics/utils.py:347-363).
+ * out (DEVICE double[B][K][8]), per batch item b and class c, with p / y = the fp32 value of prediction / truth for class c
+ * (the stored value of a channel-form side; label == c ? 1 : 0 of a label-map side, labels outside [0, K) count for no class):
+ *   [0] sum of y where p != 0 (NaN is non-zero)   [1] count of p != 0   [2] sum of y   [3] sum of y * p (fp32 product)   [4] sum of p
+ *   [5] count of p + y == 2   [6] count of p + y == 0   [7] count of p / y values that are neither 0 nor 1.
+ * Sums are fp64 (counts exact to 2^53), no atomics: the same input gives the same bits.  The two sides choose their form and
+ * dtype independently; tensors are contiguous, n = product of the spatial extents (n == 0 writes zeros), rows need no alignment.
+ * workspace: DEVICE, mh_overlap_sums_workspace_bytes(B, K, n) bytes, caller-owned (the size is host arithmetic: no GPU needed). */
+int64_t mh_overlap_sums_workspace_bytes(int B, int K, int64_t n);
+int mh_overlap_sums(const void* pred, int pred_form, int pred_dtype, const void* truth, int truth_form, int truth_dtype, int B, int K,
+                    int64_t n, void* workspace, double* out, void* stream);
+
 /* ---- Gaussian smoothing (GaussianSmooth / GaussianFilter / separable_filtering) ----------------------------- */
 
 /* dst = src convolved with kz (x) ky (x) kx, zero padding, per channel volume [NC][D][H][W]

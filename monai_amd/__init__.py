@@ -8,4 +8,6 @@ __version__ = "0.1.0"
 
 from . import _fallback as _fallback  # noqa: E402
 
+from . import metrics as metrics  # noqa: E402,F401
+
 _fallback.apply_all()      # every class falls through to the reference object of the same name for calls outside the HIP path (B3)

@@ -143,6 +143,8 @@ SIGNATURES = {
     "mh_grid_pull": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _IA, _IA, _I, _P]),
     "mh_pushpull": (_I, [_P, _P, _P, _P, _P] + [_I] * 10 + [_IA, _IA] + [_I] * 7 + [_P]),
     "mh_grid_resample_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mh_overlap_sums_workspace_bytes": (_L, [_I, _I, _L]),
+    "mh_overlap_sums": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _L, _P, _P, _P]),
 }
 
 

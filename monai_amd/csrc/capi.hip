@@ -23,6 +23,7 @@
 #include "kernels/grid_pull.h"
 #include "kernels/pushpull.h"
 #include "kernels/post.h"
+#include "kernels/metrics.h"
 #include "kernels/preproc.h"
 #include "kernels/nn_simple.h"
 #include "kernels/conv1x1_h2.h"
@@ -1671,6 +1672,82 @@ int mh_flip_permute_f32(const float* src, float* dst, int C, const int32_t* in_s
     hipLaunchKernelGGL(flip_permute_kernel, dim3((unsigned)rows, (unsigned)((out_size[2] + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, dst,
                        out_size[0], out_size[1], out_size[2], in_stride[0] * in_size3[0], base, st[0], st[1], st[2]);
     return launched("flip_permute");
+}
+
+// ------------------------------------------------------------------------------------------ segmentation metrics (overlap records)
+// blocks along a row: one 16-byte group per lane and trip at least, at most 8 workgroups per CU in the whole grid (the grid-stride loop takes the rest)
+static inline int overlap_parts_bound(int64_t n) {
+    const long long want = (n + 511) / 512;           // the narrowest group is 2 elements (int64)
+    return (int)(want < 1 ? 1 : want > OV_MAX_BLOCKS ? OV_MAX_BLOCKS : want);
+}
+static int overlap_grid_cap() {
+#ifdef MH_SIMT_EMULATOR
+    return 32;                                        // fibers on host threads: a small grid, so the tests take more than one grid-stride trip
+#else
+    static int cap = 0;
+    if (cap == 0) {
+        int cus = 0, dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+        cap = cus * 8 > OV_MAX_BLOCKS ? OV_MAX_BLOCKS : cus * 8;
+    }
+    return cap;
+#endif
+}
+
+int64_t mh_overlap_sums_workspace_bytes(int B, int K, int64_t n) {
+    if (B < 1 || K < 1 || n < 0) return fail(MH_ERR_ARG, "overlap_sums_workspace_bytes: bad argument (B %d, K %d, n %lld)", B, K, (long long)n);
+    return (int64_t)B * overlap_parts_bound(n) * K * OV_SLOTS * (int64_t)sizeof(double);
+}
+
+template <int PF, typename TP, int YF, typename TY>
+static void overlap_launch(const void* pred, const void* truth, int B, int K, long long n, double* workspace, double* out, hipStream_t stream) {
+    constexpr int V = (sizeof(TP) < sizeof(TY) ? 16 / (int)sizeof(TP) : 16 / (int)sizeof(TY));
+    constexpr int chunk = (PF == OV_CHANNEL && YF == OV_CHANNEL) ? 1 : OV_CHUNK;      // no label map to share: a class per chunk, every row with its own aligned part
+    const int chunks = (K + chunk - 1) / chunk;
+    const long long want = (n + 256LL * V - 1) / (256LL * V);
+    long long cap = overlap_grid_cap() / ((long long)chunks * B);
+    if (cap > overlap_parts_bound(n)) cap = overlap_parts_bound(n);
+    const int blocks = (int)(want < 1 ? 1 : want > cap ? (cap < 1 ? 1 : cap) : want);
+    hipLaunchKernelGGL((overlap_partial_kernel<PF, TP, YF, TY, chunk>), dim3((unsigned)blocks, (unsigned)chunks, (unsigned)B), dim3(256), 0, stream, (const TP*)pred,
+                       (const TY*)truth, K, n, workspace);
+    hipLaunchKernelGGL(overlap_final_kernel, dim3((unsigned)K, (unsigned)B), dim3(64), 0, stream, (const double*)workspace, blocks, K, out);
+}
+
+int mh_overlap_sums(const void* pred, int pred_form, int pred_dtype, const void* truth, int truth_form, int truth_dtype, int B, int K, int64_t n,
+                    void* workspace, double* out, void* stream) {
+    if (!pred || !truth || !workspace || !out) return fail(MH_ERR_ARG, "overlap_sums: null pointer");
+    if (B < 1 || K < 1 || n < 0) return fail(MH_ERR_ARG, "overlap_sums: bad argument (B %d, K %d, n %lld)", B, K, (long long)n);
+    const int forms[2] = {pred_form, truth_form}, dtypes[2] = {pred_dtype, truth_dtype};
+    for (int s = 0; s < 2; ++s) {
+        if (forms[s] != OV_CHANNEL && forms[s] != OV_LABELS) return fail(MH_ERR_ARG, "overlap_sums: unknown form %d of the %s", forms[s], s ? "truth" : "prediction");
+        if (dtypes[s] != OV_F32 && dtypes[s] != OV_U8 && dtypes[s] != OV_I64) return fail(MH_ERR_ARG, "overlap_sums: unknown dtype %d of the %s", dtypes[s], s ? "truth" : "prediction");
+        if (forms[s] == OV_CHANNEL && dtypes[s] == OV_I64) return fail(MH_ERR_ARG, "overlap_sums: a channel-form %s is float32 or uint8, not int64", s ? "truth" : "prediction");
+    }
+    if (B > 65535 || K > 65535 || n > (1LL << 48)) return fail(MH_ERR_UNSUPPORTED, "overlap_sums: problem too large for one launch");
+    const hipStream_t st = (hipStream_t)stream;
+    const long long nn = (long long)n;
+    double* ws = (double*)workspace;
+    typedef unsigned char u8;
+    typedef long long i64;
+    // (form, dtype) of a side -> 0 channel f32, 1 channel u8, 2 labels f32, 3 labels u8, 4 labels i64
+    const int sp = pred_form == OV_CHANNEL ? pred_dtype : 2 + pred_dtype, sy = truth_form == OV_CHANNEL ? truth_dtype : 2 + truth_dtype;
+#define MH_OV_TRUTH(PF_, TP_)                                                                          \
+    switch (sy) {                                                                                      \
+    case 0: overlap_launch<PF_, TP_, OV_CHANNEL, float>(pred, truth, B, K, nn, ws, out, st); break;    \
+    case 1: overlap_launch<PF_, TP_, OV_CHANNEL, u8>(pred, truth, B, K, nn, ws, out, st); break;       \
+    case 2: overlap_launch<PF_, TP_, OV_LABELS, float>(pred, truth, B, K, nn, ws, out, st); break;     \
+    case 3: overlap_launch<PF_, TP_, OV_LABELS, u8>(pred, truth, B, K, nn, ws, out, st); break;        \
+    default: overlap_launch<PF_, TP_, OV_LABELS, i64>(pred, truth, B, K, nn, ws, out, st); break;      \
+    }
+    switch (sp) {
+    case 0: MH_OV_TRUTH(OV_CHANNEL, float) break;
+    case 1: MH_OV_TRUTH(OV_CHANNEL, u8) break;
+    case 2: MH_OV_TRUTH(OV_LABELS, float) break;
+    case 3: MH_OV_TRUTH(OV_LABELS, u8) break;
+    default: MH_OV_TRUTH(OV_LABELS, i64) break;
+    }
+#undef MH_OV_TRUTH
+    return launched("overlap_sums");
 }
 
 // ------------------------------------------------------------------------------------------ Gaussian smoothing

@@ -1030,3 +1030,42 @@ def minmax_scale(src: torch.Tensor, channels: int, n: int, b_scale: Optional[flo
     L.call("mh_minmax_scale_f32", _lib.ptr(src), _lib.ptr(out), int(channels), int(n), _lib.ptr(table), int(b_scale is not None), float(b_scale or 0.0),
            float(b_min), int(flat_mul is not None), float(flat_mul or 0.0), _s(src))
     return out
+
+
+_OV_DTYPES = {torch.float32: 0, torch.uint8: 1, torch.bool: 1, torch.int64: 2}
+
+
+def overlap_sums(pred: torch.Tensor, truth: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """pred / truth [B, C, spatial...] -> DEVICE float64 [B, num_classes, 8]: the overlap record of every (batch item, class) the segmentation
+    metrics are finished from, in one pass (csrc/kernels/metrics.h; monai/metrics/meandice.py:281-337, meaniou.py:130-147,
+    confusion_matrix.py:153-176).  Each side on its own is a channel form (C == num_classes; float32 / bool / uint8 values) or a label map
+    (C == 1 != num_classes; float32 / uint8 / int64 class indices).  Slots: 0 sum of y where p != 0, 1 count of p != 0, 2 sum of y, 3 sum of y * p,
+    4 sum of p, 5 count of p + y == 2, 6 count of p + y == 0, 7 count of values that are neither 0 nor 1.  No host synchronisation."""
+    _lib.require_device(pred, truth, dtypes=tuple(_OV_DTYPES))
+    k = int(num_classes)
+    if pred.dim() < 2 or truth.dim() < 2 or pred.shape[0] != truth.shape[0] or tuple(pred.shape[2:]) != tuple(truth.shape[2:]) or k < 1:
+        raise RuntimeError(f"monai_amd.overlap_sums: [B, C, spatial...] tensors of one batch size and spatial shape required, got {tuple(pred.shape)} and {tuple(truth.shape)}")
+    if not (pred.is_contiguous() and truth.is_contiguous()):
+        raise RuntimeError("monai_amd.overlap_sums: contiguous tensors required")
+    forms = []
+    for t, who in ((pred, "pred"), (truth, "truth")):
+        if t.shape[1] == k:
+            if t.dtype == torch.int64:
+                raise _lib.UnsupportedOnDevice(f"monai_amd.overlap_sums: a channel-form {who} is float32, bool or uint8, not int64")
+            forms.append(0)
+        elif t.shape[1] == 1:
+            forms.append(1)
+        else:
+            raise RuntimeError(f"monai_amd.overlap_sums: {who} has {t.shape[1]} channels, neither 1 (a label map) nor num_classes = {k}")
+    b = int(pred.shape[0])
+    out = torch.empty((b, k, 8), dtype=torch.float64, device=pred.device)
+    if b == 0:
+        return out
+    n = 1
+    for v in pred.shape[2:]:
+        n *= int(v)
+    L = _lib.lib()
+    ws = torch.empty(L.query("mh_overlap_sums_workspace_bytes", b, k, n), dtype=torch.uint8, device=pred.device)
+    L.call("mh_overlap_sums", _lib.ptr(pred), forms[0], _OV_DTYPES[pred.dtype], _lib.ptr(truth), forms[1], _OV_DTYPES[truth.dtype], b, k, n,
+           _lib.ptr(ws), _lib.ptr(out), _s(pred))
+    return out

@@ -113,9 +113,14 @@ _TARGETS = {
     },
     "monai.networks.layers.simplelayers": {"GaussianFilter": ("monai_amd.networks.layers.simplelayers", "GaussianFilter")},
     "monai.networks.blocks.warp": {"Warp": ("monai_amd.networks.blocks.warp", "Warp"), "DVF2DDF": ("monai_amd.networks.blocks.warp", "DVF2DDF")},
+    "monai.metrics.meandice": {n: ("monai_amd.metrics.meandice", n) for n in ("DiceMetric", "compute_dice", "DiceHelper")},
+    "monai.metrics.meaniou": {n: ("monai_amd.metrics.meaniou", n) for n in ("MeanIoU", "compute_iou")},
+    "monai.metrics.confusion_matrix": {n: ("monai_amd.metrics.confusion_matrix", n) for n in
+                                       ("ConfusionMatrixMetric", "get_confusion_matrix", "compute_confusion_matrix_metric", "check_confusion_matrix_metric_name")},
+    "monai.metrics.utils": {n: ("monai_amd.metrics.utils", n) for n in ("do_metric_reduction", "ignore_background", "is_binary_tensor")},
 }
 # parent packages that re-export the names above
-_REEXPORT = ["monai.inferers", "monai.networks.nets", "monai.transforms", "monai.networks.layers", "monai.networks.blocks"]
+_REEXPORT = ["monai.inferers", "monai.networks.nets", "monai.transforms", "monai.networks.layers", "monai.networks.blocks", "monai.metrics"]
 
 _installed: dict = {}
 
