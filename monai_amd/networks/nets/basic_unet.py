@@ -26,12 +26,12 @@ from __future__ import annotations
 
 import threading
 from collections.abc import Sequence
-from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from ... import _lib, _prof, config, ops
+from .._conv_engine import ConvEngine, split_configs
 
 __all__ = ["BasicUNet", "BasicUnet", "Basicunet", "basicunet"]
 
@@ -71,19 +71,7 @@ class _ADN(nn.Module):
             if self.A.weight.numel() != 1:
                 raise NotImplementedError("monai_amd.BasicUNet: PReLU with one slope per channel is not on the HIP path yet (num_parameters=1 is)")
         else:
-            self.negative_slope_ = float(slope)
-
-    @property
-    def negative_slope(self) -> float:
-        if not hasattr(self, "A"):
-            return self.negative_slope_
-        w = self.A.weight                           # one device -> host read per parameter version, not per launch
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = getattr(self, "_slope_cache", None)
-        if hit is None or hit[0] != key:
-            hit = (key, float(w.detach().float().item()))
-            object.__setattr__(self, "_slope_cache", hit)
-        return hit[1]
+            self.negative_slope = float(slope)
 
 
 class _Convolution(nn.Module):
@@ -212,7 +200,7 @@ class BasicUNet(nn.Module):
         finally:
             _BUILD.dims = 3
         self._plans: dict = {}      # (N, D, H, W, device) -> _Plan
-        self._packed: dict = {}     # (layer name, cfg) -> (version key, packed weights)
+        self._engine = ConvEngine()
         self.fused_stats = True     # take InstanceNorm statistics from the conv epilogue when the tile kernel runs
 
     def _build(self, in_channels, out_channels, fea, kw):
@@ -227,20 +215,6 @@ class BasicUNet(nn.Module):
         self.upcat_2 = _UpCat(fea[2], fea[1], fea[1], upsample=up, **kw)
         self.upcat_1 = _UpCat(fea[1], fea[0], fea[5], halves=False, upsample=up, **kw)
         self.final_conv = _nd(nn.Conv3d, nn.Conv2d)(fea[5], out_channels, kernel_size=1)
-
-    # ---- weights ---------------------------------------------------------------------------------
-    def _packed_weight(self, name: str, conv: nn.Conv3d, cfg: int) -> torch.Tensor:
-        w = conv.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = self._packed.get((name, cfg))
-        if hit is None or hit[0] != key:
-            if w.dim() == 4:        # a 2-D kernel = the centre z-slice of a 3x3x3 one whose outer slices are zero (exact: they multiply the zero padding / nothing)
-                w3 = torch.zeros(w.shape[:2] + (3, 3, 3), dtype=w.dtype, device=w.device)
-                w3[:, :, 1] = w
-                w = w3
-            hit = (key, ops.conv3d_k3_pack(cfg, w))
-            self._packed[(name, cfg)] = hit
-        return hit[1]
 
     # ---- forward ---------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -340,75 +314,40 @@ class _Plan:
         self.sub = [e((4 if self.planar else 8) * up[l], l + 1) if self.shuffle else None for l in range(4)]
         # "nontrainable" up-sampling: the (optional) 1x1 pre-convolution's result at the lower resolution
         self.low = [e(up[l], l + 1) if self.interp else None for l in range(4)]
-        self.stats: Optional[torch.Tensor] = None
-        self.device = device
 
-    def _stats_buf(self, floats: int) -> torch.Tensor:
-        if self.stats is None or self.stats.numel() < floats:
-            self.stats = torch.empty(floats, dtype=torch.float32, device=self.device)
-        return self.stats
+    @staticmethod
+    def _slope(net, adn: _ADN) -> float:
+        """the activation's negative slope: a constant, or PReLU's one learnable weight (read once per parameter version)"""
+        return net._engine.scalar(adn.A.weight) if hasattr(adn, "A") else adn.negative_slope
 
-    def _bn_record(self, net, name: str, bn, slope: float, out_nrm) -> None:
-        """Eval-mode BatchNorm + activation as consumer-side records {alpha = weight / sqrt(running_var + eps), beta = bias - running_mean * alpha, slope, 0}:
-        a parameter fold over C values (cached per parameter version), no pass over activations, no statistics -- and no magnitude bound (0: none given)."""
-        if bn.running_mean is None or bn.running_var is None:
-            raise NotImplementedError("monai_amd.BasicUNet: BatchNorm without running statistics is not on the (inference) HIP path")
-        parts = [bn.running_mean, bn.running_var] + ([bn.weight, bn.bias] if bn.affine else [])
-        key = tuple((t.data_ptr(), t._version) for t in parts) + (slope, str(bn.running_mean.device))
-        hit = net._packed.get(("bn", name))
-        if hit is None or hit[0] != key:
-            invstd = 1.0 / torch.sqrt(bn.running_var.float() + bn.eps)
-            alpha = invstd * bn.weight.float() if bn.affine else invstd
-            beta = (bn.bias.float() if bn.affine else 0.0) - bn.running_mean.float() * alpha
-            hit = (key, torch.stack([alpha, beta, torch.full_like(alpha, slope), torch.zeros_like(alpha)], dim=1).contiguous())
-            net._packed[("bn", name)] = hit
-        out_nrm.copy_(hit[1][None].expand(out_nrm.shape[0], -1, -1))
+    def _record(self, net, block: _Convolution, raw, stats, tiles, out_nrm) -> None:
+        """the normalisation + activation behind `block`'s convolution -> records `out_nrm`: eval-mode BatchNorm is a parameter fold, Instance / GroupNorm take the
+        statistics of `raw` (the producing kernel's, or tiles 0: a pass of their own)"""
+        norm, slope = block.adn.N, self._slope(net, block.adn)
+        if self.batchnorm:
+            out_nrm.copy_(net._engine.bn_fold(norm, slope)[None].expand(out_nrm.shape[0], -1, -1))
+        else:
+            net._engine.norm_record(raw, stats, tiles, norm, slope, groups=norm.num_groups if isinstance(norm, nn.GroupNorm) else None, out=out_nrm)
 
-    def _conv(self, net, name: str, block: _Convolution, x, x_nrm, out, out_nrm, bounded: bool = True, pool_level: int = 0) -> bool:
+    def _conv(self, net, block: _Convolution, x, x_nrm, out, out_nrm, bounded: bool = True, pool_level: int = 0) -> bool:
         """conv -> raw `out`; the normalisation + activation that follows it -> records `out_nrm` ({alpha, beta, slope, bound}).  `bounded`: the input's
         records carry magnitude bounds (the split-precision convolution needs them; BatchNorm folds and interpolated tensors have none).
         `pool_level` l > 0: MaxPool3d(2) of this output feeds level l -- when the kernel can, its epilogue leaves the pooled tensor in self.pool[l] (raw maxima to be read under
         `out_nrm`; returns True) and no pooling pass runs."""
-        n, cout, d, h, w = out.shape
+        _, cout, d, h, w = out.shape
         cin = x.shape[1]
-        cfg = ops.conv3d_k3_select(cin, cout, d, h, w, bounded=x_nrm is not None and bounded and not self.batchnorm)
-        packed = net._packed_weight(name, block.conv, cfg)
-        norm = block.adn.N
-        if pool_level and block.adn.negative_slope >= 0.0 and self._poolable(net, cfg, cin, cout, d, h, w, pool_level, x_nrm):
+        bounded = x_nrm is not None and bounded and not self.batchnorm
+        pool = None
+        if (pool_level and self._slope(net, block.adn) >= 0.0
+                and self._poolable(net, ops.conv3d_k3_select(cin, cout, d, h, w, bounded=bounded), cin, cout, d, h, w, pool_level, x_nrm)):
             if self.pool_min[pool_level] is None:
                 self.pool_min[pool_level] = torch.empty_like(self.pool[pool_level])
-            tiles = ops.conv3d_k3_stat_tiles(cfg, d, h, w)
-            stats = self._stats_buf(n * cout * tiles * 3)
-            with _prof.span(f"conv3d_k3/cfg{cfg}", 2.0 * 27 * cin * cout * d * h * w * n):
-                ops.conv3d_k3_pool(cfg, x, x_nrm, packed, block.conv.bias, out, stats, self.pool[pool_level], self.pool_min[pool_level])
-            if isinstance(norm, nn.GroupNorm):
-                ops.groupnorm_finalize(stats, tiles, n, cout, norm.num_groups, norm.weight, norm.bias, norm.eps, block.adn.negative_slope, out_nrm)
-            else:
-                ops.instnorm_finalize(stats, tiles, n, cout, norm.weight, norm.bias, norm.eps, block.adn.negative_slope, out_nrm)
-            ops.pool_select(self.pool[pool_level], self.pool_min[pool_level], out_nrm)
-            return True
-        if self.batchnorm:
-            with _prof.span(f"conv3d_k3/cfg{cfg}", 2.0 * 27 * cin * cout * d * h * w * n):
-                ops.conv3d_k3(cfg, x, x_nrm, packed, block.conv.bias, out, None)
-            self._bn_record(net, name, norm, block.adn.negative_slope, out_nrm)
-            return False
-        tiles = ops.conv3d_k3_stat_tiles(cfg, d, h, w) if net.fused_stats else 0
-        flops = 2.0 * 27 * cin * cout * d * h * w * n
-        if tiles:
-            stats = self._stats_buf(n * cout * tiles * 3)
-            with _prof.span(f"conv3d_k3/cfg{cfg}", flops):
-                ops.conv3d_k3(cfg, x, x_nrm, packed, block.conv.bias, out, stats)
-        else:
-            with _prof.span(f"conv3d_k3/cfg{cfg}", flops):
-                ops.conv3d_k3(cfg, x, x_nrm, packed, block.conv.bias, out, None)
-            tiles = ops.instnorm_stat_tiles(d, h, w)
-            stats = self._stats_buf(n * cout * tiles * 3)
-            ops.instnorm_stats(out, stats)
-        if isinstance(norm, nn.GroupNorm):
-            ops.groupnorm_finalize(stats, tiles, n, cout, norm.num_groups, norm.weight, norm.bias, norm.eps, block.adn.negative_slope, out_nrm)
-        else:
-            ops.instnorm_finalize(stats, tiles, n, cout, norm.weight, norm.bias, norm.eps, block.adn.negative_slope, out_nrm)
-        return False
+            pool = (self.pool[pool_level], self.pool_min[pool_level])
+        _, stats, tiles = net._engine.conv3(block.conv, x, x_nrm, out=out, bounded=bounded, want_stats=net.fused_stats and not self.batchnorm, pool=pool)
+        self._record(net, block, out, stats, tiles, out_nrm)
+        if pool is not None:
+            ops.pool_select(*pool, out_nrm)
+        return pool is not None
 
     def _halves_cfg(self, net, l: int, cout: int, bounded: bool) -> int:
         """the configuration for `_conv_halves` at decoder level l, or -1: the concatenation's convolution is linear in its input channels, and where each 32-channel half
@@ -419,34 +358,18 @@ class _Plan:
             return -1
         _, _, d, h, w = self.cat[l].shape
         cfg = ops.conv3d_k3_select(f[l], cout, d, h, w, bounded=True)
-        if cfg != ops.conv3d_k3_h2w_config() or ops.conv3d_k3_select(2 * f[l], cout, d, h, w, bounded=True) == cfg:
+        if cfg != split_configs()[2] or ops.conv3d_k3_select(2 * f[l], cout, d, h, w, bounded=True) == cfg:
             return -1
         return cfg
 
-    def _conv_halves(self, net, name: str, block: _Convolution, l: int, cfg: int, out, out_nrm) -> None:
+    def _conv_halves(self, net, block: _Convolution, l: int, cfg: int, out, out_nrm) -> None:
         """conv(cat([x_e, x_0])) = conv[:, :f_l](x_e) + conv[:, f_l:](x_0) + b: the skip half written by the plain form, the up-sampled half added by the accumulating form together
         with the bias and the statistics of the sum.  Reference: UpCat.forward, monai/networks/nets/basic_unet.py:160-178 (torch.cat + Convolution)."""
-        f = net.features
-        fl = f[l]
-        conv = block.conv
-        n, cout, d, h, w = out.shape
-        key = (conv.weight.data_ptr(), conv.weight._version, str(conv.weight.device))
-        hit = net._packed.get(("halves", name, cfg))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.conv3d_k3_pack(cfg, conv.weight[:, :fl].contiguous()), ops.conv3d_k3_pack(cfg, conv.weight[:, fl:].contiguous()))
-            net._packed[("halves", name, cfg)] = hit
-        flops = 2.0 * 27 * fl * cout * d * h * w * n
-        with _prof.span(f"conv3d_k3/cfg{cfg}", flops):
-            ops.conv3d_k3(cfg, self.cat[l][:, :fl], self.cat_nrm[l][:, :fl], hit[1], None, out, None)
-        tiles = ops.conv3d_k3_stat_tiles(cfg, d, h, w)
-        stats = self._stats_buf(n * cout * tiles * 3)
-        with _prof.span(f"conv3d_k3/cfg{cfg}", flops):
-            ops.conv3d_k3(cfg, self.cat[l][:, fl:], self.cat_nrm[l][:, fl:], hit[2], conv.bias, out, stats, accumulate=True)
-        norm = block.adn.N
-        if isinstance(norm, nn.GroupNorm):
-            ops.groupnorm_finalize(stats, tiles, n, cout, norm.num_groups, norm.weight, norm.bias, norm.eps, block.adn.negative_slope, out_nrm)
-        else:
-            ops.instnorm_finalize(stats, tiles, n, cout, norm.weight, norm.bias, norm.eps, block.adn.negative_slope, out_nrm)
+        fl = net.features[l]
+        for half in ((0, fl), (fl, 2 * fl)):        # both halves are packed before the first launch (a level's packs precede its launches here, as in `_upcat_fused`)
+            net._engine.conv3_pack(block.conv, cfg, cin=half)
+        stats, tiles = net._engine.conv3_split(block.conv, cfg, self.cat[l], self.cat_nrm[l], fl, out, bias_on="second")
+        self._record(net, block, out, stats, tiles, out_nrm)
 
     def _poolable(self, net, cfg: int, cin: int, cout: int, d: int, h: int, w: int, level: int, x_nrm) -> bool:
         """the pooling epilogue (csrc/kernels/conv3d_h2.h, POOL): the split-precision kernel with 16 x 16 regions on even extents, a non-negative activation slope (the
@@ -472,14 +395,10 @@ class _Plan:
         hi = ops.affine_resample(low.reshape(n * c, d, h, w), m, osz, "bilinear", "border", False, False)
         dst.copy_(hi.reshape((n, c) + osz))
 
-    def _subpixel(self, net, name: str, conv: nn.Conv3d, src, src_nrm, sub, dst, dst_nrm) -> None:
+    def _subpixel(self, net, conv: nn.Conv3d, src, src_nrm, sub, dst, dst_nrm) -> None:
         """SubpixelUpsample (blocks/upsample.py:274-288): the k3 convolution of the (deferred) input to 8 x (one plane: 4 x) the up channels -- raw, no normalisation follows it -- then one pass
         that shuffles the sub-voxels into place and applies the pad + average pooling; max |value| goes into the identity records of the result"""
-        n, cin, d, h, w = src.shape
-        cout = sub.shape[1]
-        cfg = ops.conv3d_k3_select(cin, cout, d, h, w, bounded=src_nrm is not None and not self.batchnorm)
-        with _prof.span(f"conv3d_k3/cfg{cfg}", 2.0 * 27 * cin * cout * d * h * w * n):
-            ops.conv3d_k3(cfg, src, src_nrm, net._packed_weight(name, conv, cfg), conv.bias, sub, None)
+        net._engine.conv3(conv, src, src_nrm, out=sub, bounded=src_nrm is not None and not self.batchnorm, want_stats=False)
         ops.pixelshuffle(sub, dst, 1 if self.planar else 2, True, dst_nrm)
 
     def _fusable(self, net, l: int, src: torch.Tensor, cout: int) -> bool:
@@ -495,42 +414,29 @@ class _Plan:
         """conv_0(cat([x_e, deconv(x)])) = conv_0[:, :f_l](x_e) + [conv_0[:, f_l:] o deconv](x): the skip half on the 3x3x3 kernel (raw, bias included, no
         statistics), then the composite transposed convolution k4 s2 p1 of the LOW-resolution tensor added in place together with the statistics of the sum.
         Reference: UpCat.forward, monai/networks/nets/basic_unet.py:160-178."""
-        f = net.features
-        block, name = upc.convs.conv_0, f"upcat_{l + 1}.convs.conv_0"
+        f, eng = net.features, net._engine
+        block = upc.convs.conv_0
         conv, dec = block.conv, upc.upsample.deconv
         n, cout, d, h, w = out.shape
         skip, skip_nrm = self.cat[l][:, : f[l]], self.cat_nrm[l][:, : f[l]]
-        parts = [conv.weight, dec.weight] + ([dec.bias] if dec.bias is not None else [])
-        key = tuple((p_.data_ptr(), p_._version) for p_ in parts) + (str(conv.weight.device),)
         cfg = ops.conv3d_k3_select(f[l], cout, d, h, w, bounded=True)
-        hit = net._packed.get(("upcat", name, cfg))
-        if hit is None or hit[0] != key:
-            w4, table = ops.upconv_k4s2_weights(dec.weight, dec.bias, conv.weight[:, f[l]:])
-            hit = (key, ops.conv3d_k3_pack(cfg, conv.weight[:, : f[l]].contiguous()), ops.upconv_k4s2_pack(w4), table)
-            net._packed[("upcat", name, cfg)] = hit
-        _, packed_skip, packed_up, table = hit
+        packed_skip = eng.conv3_pack(conv, cfg, cin=(0, f[l]))
+        packed_up, table = eng.upconv_pack(conv, dec, f[l])
         up_flops = 2.0 * 8 * int(src.shape[1]) * cout * d * h * w * n
-        if cfg in (ops.conv3d_k3_h2_config(), ops.conv3d_k3_h2w_config()) and config.upcat_order() == "term_first":
+        h2, _, hw = split_configs()
+        if cfg in (h2, hw) and config.upcat_order() == "term_first":
             # the composite term is WRITTEN, the split-precision convolution of the skip channels adds itself to it and leaves the statistics of the sum
             with _prof.span("upconv_k4s2", up_flops):
                 ops.upconv_k4s2(src, src_nrm, packed_up, table, out, accumulate=False)
-            tiles = ops.conv3d_k3_stat_tiles(cfg, d, h, w)
-            stats = self._stats_buf(n * cout * tiles * 3)
-            with _prof.span(f"conv3d_k3/cfg{cfg}", 2.0 * 27 * f[l] * cout * d * h * w * n):
-                ops.conv3d_k3(cfg, skip, skip_nrm, packed_skip, conv.bias, out, stats, accumulate=True)
+            stats, tiles = eng.launch3(cfg, skip, skip_nrm, packed_skip, conv.bias, out, accumulate=True)
         else:
             # the convolution writes the skip half first (any kernel family), the composite term is added in place together with the statistics of the sum
-            with _prof.span(f"conv3d_k3/cfg{cfg}", 2.0 * 27 * f[l] * cout * d * h * w * n):
-                ops.conv3d_k3(cfg, skip, skip_nrm, packed_skip, conv.bias, out, None)
+            eng.launch3(cfg, skip, skip_nrm, packed_skip, conv.bias, out, want_stats=False)
             tiles = ops.upconv_k4s2_stat_tiles(*self.sp[l + 1])
-            stats = self._stats_buf(n * cout * tiles * 3)
+            stats = eng.stats_buf(n * cout * tiles * 3, out.device)
             with _prof.span("upconv_k4s2", up_flops):
                 ops.upconv_k4s2(src, src_nrm, packed_up, table, out, accumulate=True, stats=stats)
-        norm = block.adn.N
-        if isinstance(norm, nn.GroupNorm):
-            ops.groupnorm_finalize(stats, tiles, n, cout, norm.num_groups, norm.weight, norm.bias, norm.eps, block.adn.negative_slope, out_nrm)
-        else:
-            ops.instnorm_finalize(stats, tiles, n, cout, norm.weight, norm.bias, norm.eps, block.adn.negative_slope, out_nrm)
+        self._record(net, block, out, stats, tiles, out_nrm)
 
     def run(self, net: "BasicUNet", x: torch.Tensor, logits: torch.Tensor) -> None:
         f = net.features
@@ -539,8 +445,8 @@ class _Plan:
 
         # encoder
         t, tn = self.tmp[0][:, : f[0]], self.tmp_nrm[0][:, : f[0]]
-        self._conv(net, "conv_0.conv_0", net.conv_0.conv_0, x, None, t, tn)
-        pooled = self._conv(net, "conv_0.conv_1", net.conv_0.conv_1, t, tn, self.cat[0][:, : f[0]], self.cat_nrm[0][:, : f[0]], pool_level=1)
+        self._conv(net, net.conv_0.conv_0, x, None, t, tn)
+        pooled = self._conv(net, net.conv_0.conv_1, t, tn, self.cat[0][:, : f[0]], self.cat_nrm[0][:, : f[0]], pool_level=1)
         for l in range(1, 5):
             skip, skip_nrm = self.cat[l - 1][:, : f[l - 1]], self.cat_nrm[l - 1][:, : f[l - 1]]
             if pooled:      # the producing convolution left the raw maxima: read them under the skip tensor's records (act(max raw) == max(act(raw)), bit for bit)
@@ -549,12 +455,12 @@ class _Plan:
                 ops.maxpool2(skip, skip_nrm, self.pool[l], self.pool_nrm[l])
                 p_in, p_nrm = self.pool[l], self.pool_nrm[l]
             t, tn = self.tmp[l][:, : f[l]], self.tmp_nrm[l][:, : f[l]]
-            self._conv(net, f"down_{l}.convs.conv_0", downs[l].convs.conv_0, p_in, p_nrm, t, tn)
+            self._conv(net, downs[l].convs.conv_0, p_in, p_nrm, t, tn)
             if l < 4:
                 o, on = self.cat[l][:, : f[l]], self.cat_nrm[l][:, : f[l]]
             else:
                 o, on = self.x4, self.x4_nrm
-            pooled = self._conv(net, f"down_{l}.convs.conv_1", downs[l].convs.conv_1, t, tn, o, on, pool_level=l + 1 if l < 4 else 0)
+            pooled = self._conv(net, downs[l].convs.conv_1, t, tn, o, on, pool_level=l + 1 if l < 4 else 0)
 
         # decoder
         src, src_nrm = self.x4, self.x4_nrm
@@ -570,7 +476,7 @@ class _Plan:
                 if self.interp:
                     self._interpolate(upc.upsample, src, src_nrm, self.low[l], dst)
                 elif self.shuffle:
-                    self._subpixel(net, f"upcat_{l + 1}.upsample.pixelshuffle.conv_block", upc.upsample.pixelshuffle.conv_block, src, src_nrm, self.sub[l], dst, dst_nrm)
+                    self._subpixel(net, upc.upsample.pixelshuffle.conv_block, src, src_nrm, self.sub[l], dst, dst_nrm)
                 elif self.planar:     # ConvTranspose2d k2 s2 = the (1, 2, 2) kernel == stride transposed conv of the anisotropic path
                     ops.deconv_ks(src, src_nrm, _w5(upc.upsample.deconv.weight).contiguous(), upc.upsample.deconv.bias, dst, (1, 2, 2), dst_nrm)
                 else:
@@ -579,10 +485,10 @@ class _Plan:
                     ops.pad_replicate(self.up_scratch[l], self.cat[l][:, f[l]:], self.up_scratch_nrm[l], self.cat_nrm[l][:, f[l]:])
                 hcfg = self._halves_cfg(net, l, co, bounded=not self.interp)
                 if hcfg >= 0:
-                    self._conv_halves(net, f"upcat_{l + 1}.convs.conv_0", upc.convs.conv_0, l, hcfg, t, tn)
+                    self._conv_halves(net, upc.convs.conv_0, l, hcfg, t, tn)
                 else:
-                    self._conv(net, f"upcat_{l + 1}.convs.conv_0", upc.convs.conv_0, self.cat[l], self.cat_nrm[l], t, tn, bounded=not self.interp)
-            self._conv(net, f"upcat_{l + 1}.convs.conv_1", upc.convs.conv_1, t, tn, self.u[l], self.u_nrm[l])
+                    self._conv(net, upc.convs.conv_0, self.cat[l], self.cat_nrm[l], t, tn, bounded=not self.interp)
+            self._conv(net, upc.convs.conv_1, t, tn, self.u[l], self.u_nrm[l])
             src, src_nrm = self.u[l], self.u_nrm[l]
 
         fc = net.final_conv

@@ -28,7 +28,8 @@ from collections.abc import Sequence
 import torch
 import torch.nn as nn
 
-from ... import _lib, _prof, config, ops
+from ... import _lib, config, ops
+from .._conv_engine import ConvEngine, identity_records, split_configs
 
 __all__ = ["DynUNet", "DynUnet", "Dynunet"]
 
@@ -242,8 +243,7 @@ class DynUNet(nn.Module):
 
         self.skip_layers = create_skips(0, [self.input_block] + list(self.downsamples), self.upsamples[::-1],
                                         self.deep_supervision_heads if deep_supervision else None)
-        self._packed: dict = {}
-        self._stats = None
+        self._engine = ConvEngine()
 
     @staticmethod
     def initialize_weights(module):
@@ -260,125 +260,37 @@ class DynUNet(nn.Module):
         w = conv.weight
         return w if w.dim() == 5 else w.unsqueeze(2)
 
-    def _packed_weight(self, conv: nn.Conv3d, cfg: int) -> torch.Tensor:
-        w = self._w5(conv)
-        key = (w.data_ptr(), conv.weight._version, str(w.device))
-        hit = self._packed.get((id(conv), cfg))
-        if hit is None or hit[0] != key:
-            if tuple(w.shape[2:]) != (3, 3, 3):
-                # a kernel extent of 1 along an axis = a 3-tap kernel whose outer taps are zero: with padding 1 the centre tap sits on the
-                # same sample (s * o) as the reference's padding-0 extent-1 kernel.  Exact; the zero taps cost matrix time, not accuracy.
-                w3 = torch.zeros(w.shape[:2] + (3, 3, 3), dtype=w.dtype, device=w.device)
-                sl = tuple(slice(0, 3) if k == 3 else slice(1, 2) for k in w.shape[2:])
-                w3[(slice(None), slice(None)) + sl] = w
-                w = w3
-            hit = (key, ops.conv3d_k3_pack(cfg, w))
-            self._packed[(id(conv), cfg)] = hit
-        return hit[1]
-
-    def _packed_slice(self, conv: nn.Conv3d, cfg: int, c0: int, c1: int) -> torch.Tensor:
-        """packed weights of input channels c0 .. c1 - 1 of a 3x3x3 convolution (a convolution evaluated in two halves of its input channels)"""
-        w = conv.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = self._packed.get((id(conv), cfg, c0, c1))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.conv3d_k3_pack(cfg, w[:, c0:c1].contiguous()))
-            self._packed[(id(conv), cfg, c0, c1)] = hit
-        return hit[1]
-
-    def _packed_s2(self, conv: nn.Conv3d) -> torch.Tensor:
-        """the stride-2 split-precision kernel's tap matrices of a [Cout, Cin, 3, 3, 3] weight (once per parameter version)"""
-        w = conv.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = self._packed.get((id(conv), "s2"))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.conv3d_k3s2_pack(w))
-            self._packed[(id(conv), "s2")] = hit
-        return hit[1]
-
-    def _workspace(self, floats: int, device) -> torch.Tensor:
-        """scratch of the stride-2 kernel (the phase-split fp16 pieces of its input): one buffer, grown to the largest layer"""
-        ws = getattr(self, "_ws", None)
-        if ws is None or ws.numel() < floats or ws.device != device:
-            self._ws = ws = torch.empty(floats, dtype=torch.float32, device=device)
-        return ws
-
-    def _stats_buf(self, floats: int, device) -> torch.Tensor:
-        if self._stats is None or self._stats.numel() < floats or self._stats.device != device:
-            self._stats = torch.empty(floats, dtype=torch.float32, device=device)
-        return self._stats
-
-    def _finalize(self, norm: nn.InstanceNorm3d, raw, stats, tiles, slope):
-        n, c = raw.shape[:2]
-        if not tiles:
-            tiles = ops.instnorm_stat_tiles(*raw.shape[2:])
-            stats = self._stats_buf(n * c * tiles * 3, raw.device)
-            ops.instnorm_stats(raw, stats)
-        nrm = torch.empty((n, c, 4), dtype=torch.float32, device=raw.device)
-        ops.instnorm_finalize(stats, tiles, n, c, norm.weight, norm.bias, norm.eps, slope, nrm)
-        return nrm
-
     def _conv_norm(self, conv: nn.Conv3d, norm, x, x_nrm, stride, slope: float, out=None):
         """3x3x3 conv (no bias) of the (deferred) input + InstanceNorm statistics -> (raw output, {alpha, beta, slope} record); `out`: where the raw output goes (a channel
         range of a concat buffer: the skip tensor is then never materialised -- its consumers apply the record on load)"""
+        eng = self._engine
         n, cin, d, h, w = x.shape
         cout = conv.weight.shape[0]
-        sp = _out_size((d, h, w), stride)
-        if out is None:
-            out = torch.empty((n, cout) + sp, dtype=torch.float32, device=x.device)
-        tiles, stats = 0, None
-        flops = 2.0 * 27 * cin * cout * sp[0] * sp[1] * sp[2] * n
-        if stride == (1, 1, 1) and not (cin <= 8 and cout <= 8):
-            # every record of this engine carries a magnitude bound: instnorm_finalize writes one, plain tensors come with `nrm_identity` records their
-            # producers (add_act, the transposed convolutions) folded max |value| into -- what the split-precision kernel scales its input by
-            cfg = ops.conv3d_k3_select(cin, cout, d, h, w, bounded=x_nrm is not None)
-            h2 = ops.conv3d_k3_h2_config()
+        # every record of this engine carries a magnitude bound: instnorm_finalize writes one, plain tensors come with identity records their
+        # producers (add_act, the transposed convolutions) folded max |value| into -- what the split-precision kernel scales its input by
+        if stride == (1, 1, 1) and x_nrm is not None and tuple(conv.weight.shape[2:]) == (3, 3, 3) and (cin > 256 or cin == 64):
+            # a concatenation's convolution is linear in its input channels: where two halves run on a better kernel than the whole, one is written and the other
+            # added onto it by the accumulating form, which leaves the statistics of the sum
+            if out is None:
+                out = torch.empty((n, cout, d, h, w), dtype=torch.float32, device=x.device)
+            cfg = ops.conv3d_k3_select(cin, cout, d, h, w, bounded=True)
+            h2, _, hw = split_configs()
             half = (cin // 32) * 16
-            if (cfg != h2 and x_nrm is not None and tuple(conv.weight.shape[2:]) == (3, 3, 3) and cin > 256 and cin % 16 == 0
+            if (cfg != h2 and cin > 256 and cin % 16 == 0
                     and ops.conv3d_k3_select(half, cout, d, h, w, bounded=True) == h2 and ops.conv3d_k3_select(cin - half, cout, d, h, w, bounded=True) == h2):
-                # more input channels than the split-precision kernel keeps records for (the 512-channel concat of nnU-Net's 12^3 level): the convolution is linear in
-                # its input channels -- one half written, the other half added onto it by the accumulating form, which leaves the statistics of the sum
-                tiles = ops.conv3d_k3_stat_tiles(h2, d, h, w)
-                stats = self._stats_buf(n * cout * tiles * 3, x.device)
-                with _prof.span(f"conv3d_k3/cfg{h2}", flops):
-                    ops.conv3d_k3(h2, x[:, :half], x_nrm[:, :half], self._packed_slice(conv, h2, 0, half), conv.bias, out, None)
-                    ops.conv3d_k3(h2, x[:, half:], x_nrm[:, half:], self._packed_slice(conv, h2, half, cin), None, out, stats, accumulate=True)
-                return out, self._finalize(norm, out, stats, tiles, slope)
-            hw = ops.conv3d_k3_h2w_config()
-            if (cfg == h2 and cin == 64 and x_nrm is not None and tuple(conv.weight.shape[2:]) == (3, 3, 3) and config.conv_halves()
-                    and ops.conv3d_k3_select(32, cout, d, h, w, bounded=True) == hw):
-                # a 64-channel concatenation at a level whose 32-channel halves the Winograd split-precision kernel takes (the top decoder level: 64 -> 32 @ 96^3): two launches of it
-                # (plain form, then accumulating form with the statistics of the sum) cost less than one of the direct kernel -- BasicUNet._conv_halves, config.CONV_HALVES
-                tiles = ops.conv3d_k3_stat_tiles(hw, d, h, w)
-                stats = self._stats_buf(n * cout * tiles * 3, x.device)
-                with _prof.span(f"conv3d_k3/cfg{hw}", flops):
-                    ops.conv3d_k3(hw, x[:, :32], x_nrm[:, :32], self._packed_slice(conv, hw, 0, 32), None, out, None)
-                    ops.conv3d_k3(hw, x[:, 32:], x_nrm[:, 32:], self._packed_slice(conv, hw, 32, 64), conv.bias, out, stats, accumulate=True)
-                return out, self._finalize(norm, out, stats, tiles, slope)
-            tiles = ops.conv3d_k3_stat_tiles(cfg, d, h, w)
-            stats = self._stats_buf(n * cout * tiles * 3, x.device) if tiles else None
-            with _prof.span(f"conv3d_k3/cfg{cfg}", flops):
-                ops.conv3d_k3(cfg, x, x_nrm, self._packed_weight(conv, cfg), conv.bias, out, stats)
-        elif tuple(conv.weight.shape[2:]) == (3, 3, 3) and ops.conv3d_k3s2_selected(cin, cout, d, h, w, stride, bounded=x_nrm is not None):
-            # the down-sampling convolution on the fp16 matrix cores (csrc/kernels/conv3d_s2_h2.h), statistics of its output included
-            tiles = ops.conv3d_k3s2_stat_tiles(d, h, w)
-            stats = self._stats_buf(n * cout * tiles * 3, x.device)
-            with _prof.span("conv3d_k3s2", flops):
-                fused = ops.conv3d_k3s2_fused(cin, cout, d * h * w)          # conversion inside the GEMM's staging, or a phase-split pass into the workspace first
-                ops.conv3d_k3s2(x, x_nrm, self._packed_s2(conv), conv.bias, out, stats, None if fused else self._workspace(ops.conv3d_k3s2_workspace_floats(n, cin, d, h, w), x.device), fused)
-        else:       # other strides, or so few channels that the matrix tiles would mostly pad: the direct kernel at the true width
-            ops.conv3d_k3_strided3(x, x_nrm, self._packed_weight(conv, 0), conv.bias, out, stride)
-        return out, self._finalize(norm, out, stats, tiles, slope)
+                # more input channels than the split-precision kernel keeps records for (the 512-channel concat of nnU-Net's 12^3 level): two halves
+                return out, eng.norm_record(out, *eng.conv3_split(conv, h2, x, x_nrm, half, out, bias_on="first"), norm, slope)
+            if cfg == h2 and cin == 64 and config.conv_halves() and ops.conv3d_k3_select(32, cout, d, h, w, bounded=True) == hw:
+                # a 64-channel concatenation at a level whose 32-channel halves the Winograd split-precision kernel takes (the top decoder level: 64 -> 32 @ 96^3): two launches
+                # of it cost less than one of the direct kernel -- BasicUNet._conv_halves, config.CONV_HALVES
+                return out, eng.norm_record(out, *eng.conv3_split(conv, hw, x, x_nrm, 32, out, bias_on="second"), norm, slope)
+        out, stats, tiles = eng.conv3(conv, x, x_nrm, stride, out, bounded=x_nrm is not None, tiny_direct=True)
+        return out, eng.norm_record(out, stats, tiles, norm, slope)
 
     def _basic(self, blk: _Block, x, x_nrm, out=None):
         """UnetBasicBlock: conv1 -> norm1 -> lrelu -> conv2 -> norm2 -> lrelu, the last normalise + activate left to the consumer"""
         c1, n1 = self._conv_norm(blk.conv1.conv, blk.norm1, x, x_nrm, blk.stride, self._slope)
         return self._conv_norm(blk.conv2.conv, blk.norm2, c1, n1, (1, 1, 1), self._slope, out)
-
-    @staticmethod
-    def _records(t: torch.Tensor) -> torch.Tensor:
-        """fresh identity records for a plain tensor that is about to be written (its producer leaves the magnitude bounds in them)"""
-        return ops.nrm_identity(torch.empty((t.shape[0], t.shape[1], 4), dtype=torch.float32, device=t.device))
 
     def _res(self, blk: _Block, x, x_nrm, dst, dst_nrm):
         """UnetResBlock of a plain tensor (+ its identity records) into `dst` (plain): lrelu(norm2(conv2(lrelu(norm1(conv1 x)))) + shortcut)"""
@@ -392,11 +304,11 @@ class DynUNet(nn.Module):
         stats, tiles = None, 0
         if blk.stride == (1, 1, 1):
             tiles = ops.conv1x1_stat_tiles(*r.shape[2:])          # norm3's statistics come out of the shortcut convolution itself
-            stats = self._stats_buf(r.shape[0] * cout * tiles * 3, r.device)
+            stats = self._engine.stats_buf(r.shape[0] * cout * tiles * 3, r.device)
             ops.conv1x1(x, None, w3.view(cout, -1), None, r, stats)
         else:       # the strided 1x1 shortcut as the centre tap of the strided 3x3x3 kernel
-            ops.conv3d_k3_strided3(x, None, self._packed_weight(blk.conv3.conv, 0), None, r, blk.stride)
-        n3 = self._finalize(blk.norm3, r, stats, tiles, 1.0)
+            self._engine.conv3(blk.conv3.conv, x, None, blk.stride, r, bounded=False)
+        n3 = self._engine.norm_record(r, stats, tiles, blk.norm3, 1.0)
         return ops.add_act(c2, n2, r, n3, self._slope, dst, dst_nrm)
 
     def _encode(self, blk: _Block, x, x_nrm, dst, dst_nrm):
@@ -417,7 +329,7 @@ class DynUNet(nn.Module):
         n = x.shape[0]
         sp = _out_size(x.shape[2:], blk.stride)
         cat = torch.empty((n, 2 * cout) + sp, dtype=torch.float32, device=x.device)       # torch.cat((out, skip), dim=1)
-        cat_nrm = self._records(cat)
+        cat_nrm = identity_records(cat)
         skip, skip_nrm = self._encode(blk, x, x_nrm, cat[:, cout:], cat_nrm[:, cout:]), cat_nrm[:, cout:]
         if i + 1 < len(downs):
             t, tn = self._level(i + 1, skip, skip_nrm, downs, ups)

@@ -18,7 +18,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ... import _lib, _prof, config, ops
+from ... import _lib, config, ops
+from .._conv_engine import ConvEngine, accumulates, identity_records
 
 __all__ = ["SegResNet"]
 
@@ -133,77 +134,17 @@ class SegResNet(nn.Module):
         self.conv_final = nn.Sequential(_norm(kind, nargs, f), self.act_mod, _Conv(f, out_channels, k=1, bias=True))
         if dropout_prob is not None:
             self.dropout = nn.Dropout3d(dropout_prob)
-        self._packed: dict = {}
-        self._stats = None
+        self._engine = ConvEngine()
 
     # ---- helpers -----------------------------------------------------------------------------------
-    def _packed_weight(self, conv: nn.Conv3d, cfg: int) -> torch.Tensor:
-        w = conv.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = self._packed.get((id(conv), cfg))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.conv3d_k3_pack(cfg, w))
-            self._packed[(id(conv), cfg)] = hit
-        return hit[1]
-
-    def _stats_buf(self, floats: int, device) -> torch.Tensor:
-        # two live sets at most: the record set a convolution writes while its input's has already been finalised
-        if self._stats is None or self._stats.numel() < floats or self._stats.device != device:
-            self._stats = torch.empty(floats, dtype=torch.float32, device=device)
-        return self._stats
-
     def _record(self, norm, x, stats, tiles):
-        """{alpha, beta, slope} of `norm` (+ activation) for the raw tensor x; statistics from `stats` or an own pass over x"""
-        n, c = x.shape[:2]
-        if not tiles:
-            tiles = ops.instnorm_stat_tiles(*x.shape[2:])
-            stats = self._stats_buf(n * c * tiles * 3, x.device)
-            ops.instnorm_stats(x, stats)
-        nrm = torch.empty((n, c, 4), dtype=torch.float32, device=x.device)
-        groups = norm.num_groups if isinstance(norm, nn.GroupNorm) else c
-        ops.groupnorm_finalize(stats, tiles, n, c, groups, norm.weight, norm.bias, norm.eps, self._slope, nrm)
-        return nrm
+        """{alpha, beta, slope} of `norm` (+ activation) for the raw tensor x; statistics from `stats` or an own pass over x (InstanceNorm = one group per channel)"""
+        return self._engine.norm_record(x, stats, tiles, norm, self._slope, groups=norm.num_groups if isinstance(norm, nn.GroupNorm) else x.shape[1])
 
-    def _conv3(self, conv: nn.Conv3d, x, x_nrm, stride: int = 1):
-        """3x3x3 conv (no bias) of the (deferred) input -> (raw output, its statistics records or None, tiles)"""
-        n, cin, d, h, w = x.shape
-        cout = conv.weight.shape[0]
-        sp = tuple((v - 1) // stride + 1 for v in (d, h, w))
-        out = torch.empty((n, cout) + sp, dtype=torch.float32, device=x.device)
-        if stride == 1 and not (cin <= 8 and cout <= 8):
-            cfg = ops.conv3d_k3_select(cin, cout, d, h, w, bounded=x_nrm is not None)      # every record here comes from groupnorm_finalize: it carries a magnitude bound
-            tiles = ops.conv3d_k3_stat_tiles(cfg, d, h, w)
-            stats = self._stats_buf(n * cout * tiles * 3, x.device) if tiles else None
-            with _prof.span(f"conv3d_k3/cfg{cfg}", 2.0 * 27 * cin * cout * d * h * w * n):
-                ops.conv3d_k3(cfg, x, x_nrm, self._packed_weight(conv, cfg), conv.bias, out, stats)
-            return out, stats, tiles
-        if ops.conv3d_k3s2_selected(cin, cout, d, h, w, stride, bounded=x_nrm is not None):
-            # the down-sampling convolution on the fp16 matrix cores (csrc/kernels/conv3d_s2_h2.h), statistics of its output included
-            tiles = ops.conv3d_k3s2_stat_tiles(d, h, w)
-            stats = self._stats_buf(n * cout * tiles * 3, x.device)
-            with _prof.span("conv3d_k3s2", 2.0 * 27 * cin * cout * sp[0] * sp[1] * sp[2] * n):
-                fused = ops.conv3d_k3s2_fused(cin, cout, d * h * w)          # conversion inside the GEMM's staging, or a phase-split pass into the workspace first
-                ops.conv3d_k3s2(x, x_nrm, self._packed_s2(conv), conv.bias, out, stats, None if fused else self._workspace(ops.conv3d_k3s2_workspace_floats(n, cin, d, h, w), x.device), fused)
-            return out, stats, tiles
-        ops.conv3d_k3_strided(x, x_nrm, self._packed_weight(conv, 0), conv.bias, out, stride)
-        return out, None, 0
-
-    def _packed_s2(self, conv: nn.Conv3d) -> torch.Tensor:
-        """the stride-2 split-precision kernel's tap matrices of a [Cout, Cin, 3, 3, 3] weight (once per parameter version)"""
-        w = conv.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = self._packed.get((id(conv), "s2"))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.conv3d_k3s2_pack(w))
-            self._packed[(id(conv), "s2")] = hit
-        return hit[1]
-
-    def _workspace(self, floats: int, device) -> torch.Tensor:
-        """scratch of the stride-2 kernel (the phase-split fp16 pieces of its input): one buffer, grown to the largest layer"""
-        ws = getattr(self, "_ws", None)
-        if ws is None or ws.numel() < floats or ws.device != device:
-            self._ws = ws = torch.empty(floats, dtype=torch.float32, device=device)
-        return ws
+    def _conv3(self, conv: nn.Conv3d, x, x_nrm, stride: int = 1, out=None, accumulate: bool = False):
+        """3x3x3 conv (no bias) of the (deferred) input -> (raw output, its statistics records or None, tiles); every record here comes from groupnorm_finalize or a
+        residual join: it carries a magnitude bound"""
+        return self._engine.conv3(conv, x, x_nrm, stride, out, bounded=x_nrm is not None, tiny_direct=True, accumulate=accumulate)
 
     def _res_block(self, blk: _ResBlock, x, stats=None, tiles=0, out_nrm=None):
         """x + conv2(act(norm2(conv1(act(norm1 x))))) for a plain x (whose statistics records may come from its producer) -> (result, its statistics records or None, tiles).
@@ -215,16 +156,11 @@ class SegResNet(nn.Module):
         c1, s1, t1 = self._conv3(blk.conv1.conv, x, n1)
         n2 = self._record(blk.norm2, c1, s1, t1)
         conv2 = blk.conv2.conv
-        n, cin, d, h, w = c1.shape
+        _, cin, d, h, w = c1.shape
         cout = conv2.weight.shape[0]
-        if out_nrm is None and config.residual_accumulate() and not (cin <= 8 and cout <= 8):
-            cfg = ops.conv3d_k3_select(cin, cout, d, h, w, bounded=True)
-            if cfg in (ops.conv3d_k3_h2_config(), ops.conv3d_k3_h2c_config(), ops.conv3d_k3_h2w_config()):
-                tiles2 = ops.conv3d_k3_stat_tiles(cfg, d, h, w)
-                stats2 = self._stats_buf(n * cout * tiles2 * 3, x.device)
-                with _prof.span(f"conv3d_k3/cfg{cfg}", 2.0 * 27 * cin * cout * d * h * w * n):
-                    ops.conv3d_k3(cfg, c1, n2, self._packed_weight(conv2, cfg), conv2.bias, x, stats2, accumulate=True)
-                return x, stats2, tiles2
+        if (out_nrm is None and config.residual_accumulate() and not (cin <= 8 and cout <= 8)
+                and accumulates(ops.conv3d_k3_select(cin, cout, d, h, w, bounded=True))):
+            return self._conv3(conv2, c1, n2, out=x, accumulate=True)
         c2, _, _ = self._conv3(conv2, c1, n2)
         return ops.add_act(c2, None, x, None, 1.0, torch.empty_like(c2), out_nrm), None, 0
 
@@ -256,7 +192,7 @@ class SegResNet(nn.Module):
             for bi, blk in enumerate(blks):
                 feeds_down = bi == len(blks) - 1 and li + 1 < len(self.down_layers) and not isinstance(self.down_layers[li + 1][0], nn.Identity)
                 if feeds_down:
-                    t_nrm = ops.nrm_identity(torch.empty((t.shape[0], t.shape[1], 4), dtype=torch.float32, device=t.device))
+                    t_nrm = identity_records(t)
                 t, stats, tiles = self._res_block(blk, t, stats, tiles, t_nrm if feeds_down else None)
             down_x.append(t)
         down_x.reverse()

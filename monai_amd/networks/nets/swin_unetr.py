@@ -31,6 +31,7 @@ import torch.nn.functional as F
 
 from ... import _lib, _prof, config, ops
 from ...utils.misc import ensure_tuple_rep
+from .._conv_engine import ConvEngine, identity_records
 from .unetr import UNETR, _BasicBlock, _OutBlock, _trunc_normal_, _UpBlock
 
 __all__ = ["SwinUNETR"]
@@ -172,7 +173,7 @@ def _compute_mask(dims, ws, ss, device):
 
 
 class SwinUNETR(UNETR):
-    # UNETR supplies the conv-engine helpers (_conv3_in, _res_block, _tconv, _new, _packed_weight, _stats_buf); its constructor is NOT run
+    # UNETR supplies the conv-engine helpers (_conv3_in, _res_block, _tconv, _new, _lin); its constructor is NOT run
     def __init__(
         self,
         in_channels: int,
@@ -233,25 +234,20 @@ class SwinUNETR(UNETR):
         self.decoder2 = _UpBlock(2 * fs, fs)
         self.decoder1 = _UpBlock(fs, fs)
         self.out = _OutBlock(fs, out_channels)
-        self._packed: dict = {}
-        self._stats = None
-        self._bias_cache: dict = {}
+        self._engine = ConvEngine()
         self._mask_cache: dict = {}
-        self._rel_cache: dict = {}
         self._rows_cache: dict = {}
 
     # ---- Swin transformer ----------------------------------------------------------------------------------
     def _bias_t(self, attn: _WindowAttention, n: int) -> torch.Tensor:
         """relative position bias of the first n x n index entries (swin_unetr.py:524-528), per head, key-major for the kernel"""
         t = attn.relative_position_bias_table
-        key = (t.data_ptr(), t._version, str(t.device), n)
-        hit = self._bias_cache.get(id(attn))
-        if hit is None or hit[0] != key:
+
+        def build():
             idx = attn.relative_position_index[:n, :n].reshape(-1)
-            bias = t[idx].reshape(n, n, -1).permute(2, 1, 0).contiguous()       # [head][key][query]
-            hit = (key, bias)
-            self._bias_cache[id(attn)] = hit
-        return hit[1]
+            return t[idx].reshape(n, n, -1).permute(2, 1, 0).contiguous()       # [head][key][query]
+
+        return self._engine.derived((id(attn), "bias"), [t], build, n)
 
     def _mask(self, dims, ws, ss, device, regions: bool = False) -> torch.Tensor:
         """the shift mask of a (feature map, window, shift): [nW, S, S] additive table, or (regions) the int32 [nW, S] region ids it is the pairwise comparison of"""
@@ -269,16 +265,15 @@ class SwinUNETR(UNETR):
         token coordinates, index[q][k] = coord[q] - coord[k] + off with coord[t] = index[t][0], off = index[0][0] (checked once per layer and n, on the buffer
         itself: a state_dict may have replaced it) -- and the kernel that evaluates the bias from the table takes the shape; else None (the S x S table form)."""
         t, idx = attn.relative_position_bias_table, attn.relative_position_index
-        key = (idx.data_ptr(), idx._version, str(idx.device), n, t.shape[0])
-        hit = self._rel_cache.get(id(attn))
-        if hit is None or hit[0] != key:
+
+        def build():
             sub = idx[:n, :n].to(torch.int64)
             coord = sub[:, 0].contiguous()
             off = int(sub[0, 0])
             linear = bool(torch.equal(sub, coord[:, None] - coord[None, :] + off)) and int(sub.min()) >= 0 and int(sub.max()) < t.shape[0]
-            hit = (key, (coord.to(torch.int32).contiguous(), off) if linear else None)
-            self._rel_cache[id(attn)] = hit
-        return hit[1]
+            return (coord.to(torch.int32).contiguous(), off) if linear else None
+
+        return self._engine.derived((id(attn), "rel"), [idx], build, n, t.shape[0])
 
     def _rows(self, b, dims, ws, ss, device) -> torch.Tensor:
         key = (b, tuple(dims), tuple(ws), tuple(ss), str(device))
@@ -418,30 +413,30 @@ class SwinUNETR(UNETR):
             return rec.expand(t.shape[0], t.shape[1], 4).contiguous()
 
         cat1 = new(x_in, 2 * fs)                                     # decoder1 @ full resolution
-        cat1_nrm = self._records(cat1)
+        cat1_nrm = identity_records(cat1)
         self._res_block(self.encoder1.layer, x_in, None, cat1[:, fs:], cat1_nrm[:, fs:])
         cat2 = new(hs[0], 2 * fs)                                    # decoder2 @ 1/2
-        cat2_nrm = self._records(cat2)
+        cat2_nrm = identity_records(cat2)
         self._res_block(self.encoder2.layer, hs[0], hidden_records(hs[0]), cat2[:, fs:], cat2_nrm[:, fs:])
         cat3 = new(hs[1], 4 * fs)                                    # decoder3 @ 1/4
-        cat3_nrm = self._records(cat3)
+        cat3_nrm = identity_records(cat3)
         self._res_block(self.encoder3.layer, hs[1], hidden_records(hs[1]), cat3[:, 2 * fs:], cat3_nrm[:, 2 * fs:])
         cat4 = new(hs[2], 8 * fs)                                    # decoder4 @ 1/8
-        cat4_nrm = self._records(cat4)
+        cat4_nrm = identity_records(cat4)
         self._res_block(self.encoder4.layer, hs[2], hidden_records(hs[2]), cat4[:, 4 * fs:], cat4_nrm[:, 4 * fs:])
         cat5 = new(hs[3], 16 * fs)                                   # decoder5 @ 1/16: the skip is the hidden state itself
         cat5[:, 8 * fs:].copy_(hs[3])
         cat5_nrm = None
         if self.normalize:
-            cat5_nrm = self._records(cat5)
+            cat5_nrm = identity_records(cat5)
             cat5_nrm[:, 8 * fs:] = hidden_records(hs[3])
         dec4 = new(hs[4], 16 * fs)
-        dec4_nrm = self._records(dec4)          # the join leaves the bounds the transposed convolution of decoder5 scales by (csrc/kernels/deconv_h2.h)
+        dec4_nrm = identity_records(dec4)          # the join leaves the bounds the transposed convolution of decoder5 scales by (csrc/kernels/deconv_h2.h)
         self._res_block(self.encoder10.layer, hs[4], hidden_records(hs[4]), dec4, dec4_nrm)
 
         def up(blk: _UpBlock, inp, inp_nrm, cat, cat_nrm, cout, dst, head=None):
             self._tconv(blk.transp_conv.conv, inp, cat[:, :cout], None if cat_nrm is None else cat_nrm[:, :cout], inp_nrm)
-            dst_nrm = None if dst is None else self._records(dst)
+            dst_nrm = None if dst is None else identity_records(dst)
             return self._res_block(blk.conv_block, cat, cat_nrm, dst, dst_nrm, head=head), dst_nrm
 
         dec3, dec3_nrm = up(self.decoder5, dec4, dec4_nrm, cat5, cat5_nrm, 8 * fs, new(cat5, 8 * fs))

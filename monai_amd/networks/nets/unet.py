@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib, ops
+from .._conv_engine import ConvEngine, identity_records
 
 __all__ = ["UNet", "Unet"]
 
@@ -152,9 +153,7 @@ class UNet(nn.Module):
             self._create_model(in_channels, out_channels, num_res_units, bias, affine)
         finally:
             del _ADN_SPEC.v
-        self._packed: dict = {}
-        self._slopes: dict = {}
-        self._stats = None
+        self._engine = ConvEngine()
 
     def _create_model(self, in_channels, out_channels, num_res_units, bias, affine) -> None:
         def down(cin, cout, s):
@@ -183,15 +182,6 @@ class UNet(nn.Module):
         self.model = create(in_channels, out_channels, self.channels, self.strides, True)
 
     # ---- helpers -----------------------------------------------------------------------------------
-    def _packed_weight(self, conv: nn.Conv3d, cfg: int) -> torch.Tensor:
-        w = conv.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = self._packed.get((id(conv), cfg))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.conv3d_k3_pack(cfg, w))
-            self._packed[(id(conv), cfg)] = hit
-        return hit[1]
-
     def _slope(self, adn: _ADN) -> float:
         """the activation of an ADN as the slope of `y > 0 ? y : slope * y`: PReLU's weight, LeakyReLU's negative_slope, 0 for ReLU, 1 (identity) without an activation"""
         act = getattr(adn, "A", None)
@@ -201,41 +191,9 @@ class UNet(nn.Module):
             return 0.0
         if isinstance(act, nn.LeakyReLU):
             return float(act.negative_slope)
-        w = act.weight
-        if w.numel() != 1:
+        if act.weight.numel() != 1:
             raise NotImplementedError("monai_amd.UNet: per-channel PReLU is not on the HIP path")
-        key = (w.data_ptr(), w._version)
-        hit = self._slopes.get(id(act))
-        if hit is None or hit[0] != key:
-            hit = (key, float(w.detach().cpu()))     # one host read per weight version
-            self._slopes[id(act)] = hit
-        return hit[1]
-
-    def _act_record(self, slope: float, n: int, c: int, device) -> torch.Tensor:
-        """[n, c, 4] records {1, 0, slope, 0}: the bare activation (no normalisation in front of it; no magnitude bound)"""
-        hit = self._packed.get(("act", slope, n, c, str(device)))
-        if hit is None:
-            hit = torch.tensor([1.0, 0.0, slope, 0.0], dtype=torch.float32, device=device).repeat(n, c, 1).contiguous()
-            self._packed[("act", slope, n, c, str(device))] = hit
-        return hit
-
-    def _bn_record(self, bn: nn.BatchNorm3d, slope: float, n: int) -> torch.Tensor:
-        """Eval-mode BatchNorm3d + PReLU as the consumer-side record [n, C, 4] = {alpha, beta, slope, 0}: alpha = weight / sqrt(running_var
-        + eps), beta = bias - running_mean * alpha -- the x * alpha + beta form of ATen's CPU batch norm.  A parameter fold over C values
-        (cached per parameter version), not a pass over activations."""
-        if bn.running_mean is None or bn.running_var is None:
-            raise NotImplementedError("monai_amd.UNet: BatchNorm without running statistics is not on the (inference) HIP path")
-        parts = [bn.running_mean, bn.running_var] + ([bn.weight, bn.bias] if bn.affine else [])
-        key = tuple((t.data_ptr(), t._version) for t in parts) + (slope, str(bn.running_mean.device))
-        hit = self._packed.get(("bn", id(bn)))
-        if hit is None or hit[0] != key:
-            invstd = 1.0 / torch.sqrt(bn.running_var.float() + bn.eps)
-            alpha = invstd * bn.weight.float() if bn.affine else invstd
-            beta = (bn.bias.float() if bn.affine else 0.0) - bn.running_mean.float() * alpha
-            tab = torch.stack([alpha, beta, torch.full_like(alpha, slope), torch.zeros_like(alpha)], dim=1).contiguous()
-            hit = (key, tab)
-            self._packed[("bn", id(bn))] = hit
-        return hit[1].unsqueeze(0).expand(n, -1, -1).contiguous()
+        return self._engine.scalar(act.weight)
 
     def _has_batchnorm(self) -> bool:
         """BatchNorm anywhere in the net, or ADN blocks without a normalisation (their records carry no magnitude bounds: the exact-fp32 convolutions take them) --
@@ -245,84 +203,38 @@ class UNet(nn.Module):
             hit = self.__dict__["_bn_cached"] = any(isinstance(m, nn.BatchNorm3d) or (isinstance(m, _ADN) and not hasattr(m, "N")) for m in self.modules())
         return hit
 
-    def _stats_buf(self, floats: int, device) -> torch.Tensor:
-        if self._stats is None or self._stats.numel() < floats or self._stats.device != device:
-            self._stats = torch.empty(floats, dtype=torch.float32, device=device)
-        return self._stats
+    def _conv3(self, conv: nn.Conv3d, x, x_nrm, stride: int, want_stats: bool = False):
+        """3x3x3 conv (+bias) of the (deferred) input -> (raw output, statistics records, tiles).  Records written by instnorm_finalize and the identity records the
+        residual joins leave carry magnitude bounds (the split-precision kernels need them); folded BatchNorm records do not"""
+        return self._engine.conv3(conv, x, x_nrm, stride, bounded=x_nrm is not None and not self._has_batchnorm(), want_stats=want_stats, tiny_direct=True)
 
     def _conv_unit(self, unit: _Convolution, x, x_nrm):
         """`Convolution`: conv (+bias) of the (deferred) input -> (raw output, {alpha, beta, slope} record or None)."""
-        n, cin, d, h, w = x.shape
+        n, _, d, h, w = x.shape
         conv = unit.conv
         s = unit.strides
+        stats, tiles = None, 0
         if unit.is_transposed:
             cout = conv.weight.shape[1]
             out = torch.empty((n, cout, d * s, h * s, w * s), dtype=torch.float32, device=x.device)
             ops.deconv_k3(x, x_nrm, conv.weight, conv.bias, out, s)
-            stats_tiles = 0
         else:
             cout = conv.weight.shape[0]
-            do, ho, wo = (d - 1) // s + 1, (h - 1) // s + 1, (w - 1) // s + 1
-            out = torch.empty((n, cout, do, ho, wo), dtype=torch.float32, device=x.device)
-            # few channels on both sides (the 5-class top level): the matrix tiles would pad them to 32; the direct kernel runs at
-            # the channels' true width
-            tiny = s == 1 and cin <= 8 and cout <= 8
-            # records written by instnorm_finalize carry magnitude bounds (the split-precision kernel needs them); folded BatchNorm records do not
-            bounded = x_nrm is not None and not self._has_batchnorm()
-            cfg = ops.conv3d_k3_select(cin, cout, d, h, w, bounded=bounded) if (s == 1 and not tiny) else 0
             wants_stats = hasattr(unit, "adn") and hasattr(unit.adn, "N") and not isinstance(unit.adn.N, nn.BatchNorm3d) and not unit.adn.act_first
-            stats_tiles = ops.conv3d_k3_stat_tiles(cfg, d, h, w) if (s == 1 and not tiny and wants_stats) else 0
-            if s == 1 and not tiny:
-                stats = self._stats_buf(n * cout * stats_tiles * 3, x.device) if stats_tiles else None
-                ops.conv3d_k3(cfg, x, x_nrm, self._packed_weight(conv, cfg), conv.bias, out, stats)
-            elif s == 2 and bounded and ops.conv3d_k3s2_selected(cin, cout, d, h, w, s, bounded=True):
-                # the down-sampling convolution on the fp16 matrix cores (csrc/kernels/conv3d_s2_h2.h), the statistics of its output included (round 6: plain tensors of this
-                # engine carry identity records with magnitude bounds, left by the residual joins that write them)
-                tiles_ = ops.conv3d_k3s2_stat_tiles(d, h, w)
-                stats = self._stats_buf(n * cout * tiles_ * 3, x.device)
-                self._conv_s2(conv, x, x_nrm, out, stats)
-                stats_tiles = tiles_ if wants_stats else 0
-            else:
-                ops.conv3d_k3_strided(x, x_nrm, self._packed_weight(conv, 0), conv.bias, out, s)
+            out, stats, tiles = self._conv3(conv, x, x_nrm, s, wants_stats)
         if not hasattr(unit, "adn"):
             return out, None
         adn = unit.adn
         slope = self._slope(adn)
         if not hasattr(adn, "N"):                   # "A" / "DA" / "D": the bare activation as a record
-            return out, (self._act_record(slope, n, cout, x.device) if slope != 1.0 else None)
+            return out, (self._engine.act_records(slope, n, cout, x.device) if slope != 1.0 else None)
         if adn.act_first:                           # "AN...": activate, THEN normalise -- the statistics are those of the activated tensor
             if slope != 1.0:
-                out = ops.add_act(out, self._act_record(slope, n, cout, x.device), None, None, 1.0, torch.empty_like(out))
-            stats_tiles, slope = 0, 1.0
-        if isinstance(adn.N, nn.BatchNorm3d):
-            return out, self._bn_record(adn.N, slope, n)
-        if not stats_tiles:
-            stats_tiles = ops.instnorm_stat_tiles(*out.shape[2:])
-            stats = self._stats_buf(n * cout * stats_tiles * 3, x.device)
-            ops.instnorm_stats(out, stats)
-        nrm = torch.empty((n, cout, 4), dtype=torch.float32, device=x.device)
-        inorm = unit.adn.N
-        ops.instnorm_finalize(stats, stats_tiles, n, cout, inorm.weight, inorm.bias, inorm.eps, slope, nrm)
-        return out, nrm
-
-    def _conv_s2(self, conv: nn.Conv3d, x, x_nrm, out, stats) -> None:
-        """3x3x3 stride-2 convolution of a bounded input on the split-precision stride-2 kernel; `stats`: the InstanceNorm statistics of `out`"""
-        n, cin, d, h, w = x.shape
-        cout = conv.weight.shape[0]
-        wt = conv.weight
-        key = (wt.data_ptr(), wt._version, str(wt.device))
-        hit = self._packed.get((id(conv), "s2"))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.conv3d_k3s2_pack(wt))
-            self._packed[(id(conv), "s2")] = hit
-        fused = ops.conv3d_k3s2_fused(cin, cout, d * h * w)          # conversion inside the GEMM's staging, or a phase-split pass into the workspace first
-        ws = None
-        if not fused:
-            need = ops.conv3d_k3s2_workspace_floats(n, cin, d, h, w)
-            ws = self.__dict__.get("_ws")
-            if ws is None or ws.numel() < need or ws.device != x.device:
-                ws = self.__dict__["_ws"] = torch.empty(need, dtype=torch.float32, device=x.device)
-        ops.conv3d_k3s2(x, x_nrm, hit[1], conv.bias, out, stats, ws, fused)
+                out = ops.add_act(out, self._engine.act_records(slope, n, cout, x.device), None, None, 1.0, torch.empty_like(out))
+            tiles, slope = 0, 1.0
+        if isinstance(adn.N, nn.BatchNorm3d):       # eval-mode BatchNorm3d + activation IS the consumer-side record: a parameter fold, not a pass over activations
+            return out, self._engine.bn_fold(adn.N, slope).unsqueeze(0).expand(n, -1, -1).contiguous()
+        return out, self._engine.norm_record(out, stats, tiles, adn.N, slope)
 
     def _residual_unit(self, ru: _ResidualUnit, x, x_nrm, dst, dst_nrm=None):
         """cx + res into `dst` (plain; dst_nrm: its `nrm_identity` records, the join leaves the magnitude bounds in them).  `x` may be deferred (raw + record): both the
@@ -335,12 +247,7 @@ class UNet(nn.Module):
             cout = rc.weight.shape[0]
             s = ru.strides
             if rc.kernel_size[0] == 3:
-                cin, d, h, w = x.shape[1:]
-                res = torch.empty((n, cout) + tuple((v - 1) // s + 1 for v in x.shape[2:]), dtype=torch.float32, device=x.device)
-                if s == 2 and x_nrm is not None and not self._has_batchnorm() and ops.conv3d_k3s2_selected(cin, cout, d, h, w, s, bounded=True):
-                    self._conv_s2(rc, x, x_nrm, res, self._stats_buf(n * cout * ops.conv3d_k3s2_stat_tiles(d, h, w) * 3, x.device))
-                else:
-                    ops.conv3d_k3_strided(x, x_nrm, self._packed_weight(rc, 0), rc.bias, res, s)
+                res, _, _ = self._conv3(rc, x, x_nrm, s)
             else:
                 res = torch.empty((n, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
                 ops.conv1x1(x, x_nrm, rc.weight.view(cout, -1), rc.bias, res)
@@ -385,7 +292,7 @@ class UNet(nn.Module):
         cs = self._out_channels(sub[2]) if isinstance(sub, nn.Sequential) and isinstance(sub[1], _SkipConnection) else self._out_channels(sub)
         cat = torch.empty((n, cd + cs) + sp, dtype=torch.float32, device=x.device)      # SkipConnection: cat([x, sub(x)], 1)
         # the down path's joins leave max |value| in identity records of their results: the next level's strided convolutions run on the matrix cores with them
-        d_nrm = None if self._has_batchnorm() else ops.nrm_identity(torch.empty((n, cd, 4), dtype=torch.float32, device=x.device))
+        d_nrm = None if self._has_batchnorm() else identity_records(cat[:, :cd])
         d = self._down(down, x, cat[:, :cd], x_nrm, d_nrm)
         if isinstance(sub, nn.Sequential) and isinstance(sub[1], _SkipConnection):
             self._block(sub, d, cat[:, cd:], d_nrm)

@@ -23,6 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import _lib, _prof, ops
+from .._conv_engine import ConvEngine, identity_records, split_configs
 from ...utils.misc import ensure_tuple_rep
 
 __all__ = ["UNETR"]
@@ -208,90 +209,38 @@ class UNETR(nn.Module):
         self.decoder3 = _UpBlock(fs * 4, fs * 2, res_block)
         self.decoder2 = _UpBlock(fs * 2, fs, res_block)
         self.out = _OutBlock(fs, out_channels)
-        self._packed: dict = {}
-        self._stats = None
+        self._engine = ConvEngine()
 
     # ---- helpers -----------------------------------------------------------------------------------
-    def _packed_weight(self, conv: nn.Conv3d, cfg: int, part=None) -> torch.Tensor:
-        """the layer's weights packed for configuration `cfg` (cached; re-packed when the parameter changed); `part` = (lo, hi): output channels lo .. hi - 1 only"""
-        w = conv.weight
-        key = (w.data_ptr(), w._version, str(w.device), cfg, part)
-        slot = id(conv) if part is None else (id(conv), part)
-        hit = self._packed.get(slot)
-        if hit is None or hit[0] != key:
-            hit = (key, ops.conv3d_k3_pack(cfg, w if part is None else w[part[0]:part[1]]))
-            self._packed[slot] = hit
-        return hit[1]
-
-    def _packed_cin(self, conv: nn.Conv3d, cfg: int, c0: int, c1: int) -> torch.Tensor:
-        """packed weights of INPUT channels c0 .. c1 - 1 (a convolution evaluated in two halves of its input channels)"""
-        w = conv.weight
-        key = (w.data_ptr(), w._version, str(w.device), cfg)
-        slot = (id(conv), "cin", c0, c1)
-        hit = self._packed.get(slot)
-        if hit is None or hit[0] != key:
-            hit = (key, ops.conv3d_k3_pack(cfg, w[:, c0:c1].contiguous()))
-            self._packed[slot] = hit
-        return hit[1]
-
-    def _stats_buf(self, floats: int, device) -> torch.Tensor:
-        if self._stats is None or self._stats.numel() < floats or self._stats.device != device:
-            self._stats = torch.empty(floats, dtype=torch.float32, device=device)
-        return self._stats
-
     def _conv3_in(self, conv: nn.Conv3d, x, x_nrm, slope: float):
         """3x3x3 conv (no bias) + InstanceNorm(no affine) statistics -> (raw output, its {alpha, beta, slope} record)."""
+        eng = self._engine
         n, cin, d, h, w = x.shape
         cout = conv.weight.shape[0]
-        # every record of this engine carries a magnitude bound (instnorm_finalize writes one; plain tensors come with `nrm_identity` records that their
+        # every record of this engine carries a magnitude bound (instnorm_finalize writes one; plain tensors come with identity records that their
         # producers -- add_act, the transposed convolutions -- folded max |value| into): what the split-precision kernel scales its input by
-        cfg = ops.conv3d_k3_select(cin, cout, d, h, w, bounded=x_nrm is not None)
-        out = torch.empty((n, cout, d, h, w), dtype=torch.float32, device=x.device)
-        nrm = torch.empty((n, cout, 4), dtype=torch.float32, device=x.device)
-        h2, h2c = ops.conv3d_k3_h2_config(), ops.conv3d_k3_h2c_config()
-        if cfg == h2 and cout % 32 == 16 and ops.conv3d_k3_accepts(h2c, cin, 16):
-            # 48, 80, ... couts on the split-precision kernel (SwinUNETR(48)'s full-resolution levels): the last 16 as a group of their own in the 16-couts form (6
-            # matrix instructions per tap) instead of a half-filled group of 32 (9): two launches into channel slices, two statistics sets (same tile count)
-            tiles = ops.conv3d_k3_stat_tiles(h2, d, h, w)
-            stats = self._stats_buf(n * cout * tiles * 3, x.device)
-            lo = 0
-            for part_cfg, hi in ((h2, cout - 16), (h2c, cout)):
-                st = stats[n * lo * tiles * 3:n * hi * tiles * 3]
-                with _prof.span(f"conv3d_k3/cfg{part_cfg}", 2.0 * 27 * cin * (hi - lo) * d * h * w * n):
-                    ops.conv3d_k3(part_cfg, x, x_nrm, self._packed_weight(conv, part_cfg, (lo, hi)), None, out[:, lo:hi], st)
-                ops.instnorm_finalize(st, tiles, n, hi - lo, None, None, 1e-5, slope, nrm[:, lo:hi])
-                lo = hi
-            return out, nrm
-        flops = 2.0 * 27 * cin * cout * d * h * w * n
-        half = (cin // 32) * 16
-        if (cfg not in (h2, h2c) and x_nrm is not None and cin > 256 and cin % 16 == 0 and cout % 32 == 0
-                and ops.conv3d_k3_select(half, cout, d, h, w, bounded=True) == h2 and ops.conv3d_k3_select(cin - half, cout, d, h, w, bounded=True) == h2):
-            # more input channels than the split-precision kernel keeps records for (SwinUNETR(48)'s 384-channel concat at 12^3): the convolution is linear in its input
-            # channels -- one half written, the other half added onto it by the accumulating form, which leaves the statistics of the sum
-            tiles = ops.conv3d_k3_stat_tiles(h2, d, h, w)
-            stats = self._stats_buf(n * cout * tiles * 3, x.device)
-            with _prof.span(f"conv3d_k3/cfg{h2}", flops):
-                ops.conv3d_k3(h2, x[:, :half], x_nrm[:, :half], self._packed_cin(conv, h2, 0, half), None, out, None)
-                ops.conv3d_k3(h2, x[:, half:], x_nrm[:, half:], self._packed_cin(conv, h2, half, cin), None, out, stats, accumulate=True)
-            ops.instnorm_finalize(stats, tiles, n, cout, None, None, 1e-5, slope, nrm)
-            return out, nrm
-        tiles = ops.conv3d_k3_stat_tiles(cfg, d, h, w)
-        if tiles:
-            stats = self._stats_buf(n * cout * tiles * 3, x.device)
-            with _prof.span(f"conv3d_k3/cfg{cfg}", flops):
-                ops.conv3d_k3(cfg, x, x_nrm, self._packed_weight(conv, cfg), None, out, stats)
-        else:
-            ops.conv3d_k3(cfg, x, x_nrm, self._packed_weight(conv, cfg), None, out, None)
-            tiles = ops.instnorm_stat_tiles(d, h, w)
-            stats = self._stats_buf(n * cout * tiles * 3, x.device)
-            ops.instnorm_stats(out, stats)
-        ops.instnorm_finalize(stats, tiles, n, cout, None, None, 1e-5, slope, nrm)
-        return out, nrm
-
-    @staticmethod
-    def _records(t: torch.Tensor) -> torch.Tensor:
-        """fresh identity records for a plain tensor that is about to be written (its producers leave the magnitude bounds in them)"""
-        return ops.nrm_identity(torch.empty((t.shape[0], t.shape[1], 4), dtype=torch.float32, device=t.device))
+        if x_nrm is not None and (cout % 32 == 16 or cin > 256):
+            cfg = ops.conv3d_k3_select(cin, cout, d, h, w, bounded=True)
+            h2, h2c, _ = split_configs()
+            out = torch.empty((n, cout, d, h, w), dtype=torch.float32, device=x.device)
+            if cfg == h2 and cout % 32 == 16 and ops.conv3d_k3_accepts(h2c, cin, 16):
+                # 48, 80, ... couts on the split-precision kernel (SwinUNETR(48)'s full-resolution levels): the last 16 as a group of their own in the 16-couts form (6
+                # matrix instructions per tap) instead of a half-filled group of 32 (9): two launches into channel slices, two statistics sets (same tile count)
+                nrm = torch.empty((n, cout, 4), dtype=torch.float32, device=x.device)
+                stats, tiles = eng.epilogue_stats(h2, out)
+                per_channel = n * tiles * 3
+                for part_cfg, lo, hi in ((h2, 0, cout - 16), (h2c, cout - 16, cout)):
+                    st, tiles = eng.launch3(part_cfg, x, x_nrm, eng.conv3_pack(conv, part_cfg, cout=(lo, hi)), None, out[:, lo:hi], stats=stats[lo * per_channel:hi * per_channel])
+                    eng.norm_record(out[:, lo:hi], st, tiles, None, slope, out=nrm[:, lo:hi])
+                return out, nrm
+            half = (cin // 32) * 16
+            if (cfg not in (h2, h2c) and cin > 256 and cin % 16 == 0 and cout % 32 == 0
+                    and ops.conv3d_k3_select(half, cout, d, h, w, bounded=True) == h2 and ops.conv3d_k3_select(cin - half, cout, d, h, w, bounded=True) == h2):
+                # more input channels than the split-precision kernel keeps records for (SwinUNETR(48)'s 384-channel concat at 12^3): the convolution is linear in its input
+                # channels -- one half written, the other half added onto it by the accumulating form, which leaves the statistics of the sum
+                return out, eng.norm_record(out, *eng.conv3_split(conv, h2, x, x_nrm, half, out, bias_on=None), None, slope)
+        out, stats, tiles = eng.conv3(conv, x, x_nrm, bounded=x_nrm is not None)
+        return out, eng.norm_record(out, stats, tiles, None, slope)
 
     def _res_block(self, blk: _ResBlock, x, x_nrm, out, out_nrm, head=None):
         """UnetResBlock (dynunet_block.py:96-111) of a plain (already activated) tensor `x` (+ its identity records, or None) into `out`.
@@ -309,19 +258,13 @@ class UNETR(nn.Module):
             n, cout = x.shape[0], w3.shape[0]
             r = torch.empty((n, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
             tiles = ops.conv1x1_stat_tiles(*x.shape[2:])          # norm3's statistics come out of the shortcut convolution itself
-            stats = self._stats_buf(n * cout * tiles * 3, x.device)
+            stats = self._engine.stats_buf(n * cout * tiles * 3, x.device)
             if x_nrm is not None and cout > 16 and ops.conv1x1_h2_wanted(x.shape[1], cout, *x.shape[2:]):
                 # more than one group of 16 output channels: all of them from ONE read of x on the matrix cores (kernels/conv1x1_h2.h; x's records carry the bounds)
-                key = (w3.data_ptr(), w3._version, str(w3.device))
-                hit = self._packed.get(("1x1", id(blk.conv3.conv)))
-                if hit is None or hit[0] != key:
-                    hit = (key, ops.conv1x1_h2_pack(w3.view(cout, -1)))
-                    self._packed[("1x1", id(blk.conv3.conv))] = hit
-                ops.conv1x1_h2(x, x_nrm, hit[1], None, r, stats)
+                ops.conv1x1_h2(x, x_nrm, self._engine.conv1x1_h2_pack(blk.conv3.conv), None, r, stats)
             else:
                 ops.conv1x1(x, None, w3.view(cout, -1), None, r, stats)
-            n3 = torch.empty((n, cout, 4), dtype=torch.float32, device=x.device)
-            ops.instnorm_finalize(stats, tiles, n, cout, None, None, 1e-5, 1.0, n3)
+            n3 = self._engine.norm_record(r, stats, tiles, None, 1.0)
             res, res_nrm = r, n3
         else:
             res, res_nrm = x, None
@@ -365,16 +308,12 @@ class UNETR(nn.Module):
         """nn.Linear (+ GELU) (+ residual) as ONE launch of the split-precision GEMM kernel (csrc/kernels/dense.h); the packed weight
         is cached per parameter (re-packed when the parameter is updated in place or moved).  scatter: int32 row map -- row m of the result lands in (and takes its
         residual from) row scatter[m] of a tensor shaped like `residual` (ops.linear_scatter)."""
-        key = (weight.data_ptr(), weight._version, str(weight.device))
-        hit = self._packed.get(("lin", id(weight)))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.linear_pack(weight.reshape(weight.shape[0], -1)))
-            self._packed[("lin", id(weight))] = hit
+        packed = self._engine.linear_pack(weight)
         m = x.numel() // x.shape[-1]
         with _prof.span("linear", 2.0 * m * weight.shape[0] * x.shape[-1]):
             if scatter is not None:
-                return ops.linear_scatter(x, hit[1], weight.shape[0], bias, residual, scatter, gelu=gelu)
-            return ops.linear(x, hit[1], weight.shape[0], bias, residual, gelu=gelu)
+                return ops.linear_scatter(x, packed, weight.shape[0], bias, residual, scatter, gelu=gelu)
+            return ops.linear(x, packed, weight.shape[0], bias, residual, gelu=gelu)
 
     def _vit(self, x_in):
         """ViT (monai/networks/nets/vit.py:27-142): patch embedding, 12 x TransformerBlock (transformerblock.py:88-105: x + attn(norm1(x)),
@@ -431,7 +370,7 @@ class UNETR(nn.Module):
 
         # decoder concat buffers: [upsampled | skip], each with identity records its producers fold their magnitude bounds into
         cat2 = self._new(x_in, 2 * fs)                       # decoder2 @ full resolution
-        cat2_nrm = self._records(cat2)
+        cat2_nrm = identity_records(cat2)
         self._res_block(self.encoder1.layer, x_in, None, cat2[:, fs:], cat2_nrm[:, fs:])
 
         def prup(blk: _PrUpBlock, t, dst, dst_nrm):
@@ -439,41 +378,41 @@ class UNETR(nn.Module):
             cout = blk.transp_conv_init.conv.weight.shape[1]
             direct = len(blk.blocks) == 0
             cur = dst if direct else self._new(t, cout, 2)
-            cur_nrm = dst_nrm if direct else self._records(cur)
+            cur_nrm = dst_nrm if direct else identity_records(cur)
             self._tconv(blk.transp_conv_init.conv, t, cur, cur_nrm, self._bounded(t))
             for i, seq in enumerate(blk.blocks):
                 last = i == len(blk.blocks) - 1
                 if not isinstance(seq, nn.Sequential):        # conv_block=False: the bare transposed convolution
                     nxt = dst if last else self._new(cur, cout, 2)
-                    nxt_nrm = dst_nrm if last else self._records(nxt)
+                    nxt_nrm = dst_nrm if last else identity_records(nxt)
                     self._tconv(seq.conv, cur, nxt, nxt_nrm, cur_nrm)
                     cur, cur_nrm = nxt, nxt_nrm
                     continue
                 up = self._new(cur, cout, 2)
-                up_nrm = self._records(up)
+                up_nrm = identity_records(up)
                 self._tconv(seq[0].conv, cur, up, up_nrm, cur_nrm)
                 nxt = dst if last else self._new(up, cout)
-                nxt_nrm = dst_nrm if last else self._records(nxt)
+                nxt_nrm = dst_nrm if last else identity_records(nxt)
                 self._res_block(seq[1], up, up_nrm, nxt, nxt_nrm)
                 cur, cur_nrm = nxt, nxt_nrm
             return cur
 
         p2 = self._proj_feat(hs[3])
         cat3 = self._new(p2, 4 * fs, 8)                      # decoder3 @ 1/2 resolution
-        cat3_nrm = self._records(cat3)
+        cat3_nrm = identity_records(cat3)
         prup(self.encoder2, p2, cat3[:, 2 * fs:], cat3_nrm[:, 2 * fs:])
         p3 = self._proj_feat(hs[6])
         cat4 = self._new(p3, 8 * fs, 4)                      # decoder4 @ 1/4
-        cat4_nrm = self._records(cat4)
+        cat4_nrm = identity_records(cat4)
         prup(self.encoder3, p3, cat4[:, 4 * fs:], cat4_nrm[:, 4 * fs:])
         p4 = self._proj_feat(hs[9])
         cat5 = self._new(p4, 16 * fs, 2)                     # decoder5 @ 1/8
-        cat5_nrm = self._records(cat5)
+        cat5_nrm = identity_records(cat5)
         prup(self.encoder4, p4, cat5[:, 8 * fs:], cat5_nrm[:, 8 * fs:])
 
         def up(blk: _UpBlock, inp, inp_nrm, cat, cat_nrm, cout, dst, head=None):
             self._tconv(blk.transp_conv.conv, inp, cat[:, :cout], cat_nrm[:, :cout], inp_nrm)
-            dst_nrm = None if dst is None else self._records(dst)          # the block's join leaves the bounds the next level's transposed convolution scales by
+            dst_nrm = None if dst is None else identity_records(dst)          # the block's join leaves the bounds the next level's transposed convolution scales by
             return self._res_block(blk.conv_block, cat, cat_nrm, dst, dst_nrm, head=head), dst_nrm
 
         xf = self._proj_feat(x)

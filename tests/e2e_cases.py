@@ -801,6 +801,7 @@ def case_conv_cout_16_mod_32_split(device, cin=32, cout=48, dims=(6, 16, 16), n=
 
     import kernel_cases as kc
     from monai_amd import config, ops
+    from monai_amd.networks._conv_engine import ConvEngine
     from monai_amd.networks.nets import UNETR
 
     gen = torch.Generator().manual_seed(77)
@@ -822,8 +823,8 @@ def case_conv_cout_16_mod_32_split(device, cin=32, cout=48, dims=(6, 16, 16), n=
     ops.conv3d_k3 = spy
     try:
         for algo in ("auto", "fp32"):
-            eng = object.__new__(UNETR)          # the conv-engine helpers need only these two attributes
-            eng._packed, eng._stats = {}, None
+            eng = object.__new__(UNETR)          # the conv-engine helpers need only this attribute
+            eng._engine = ConvEngine()
             seen.clear()
             with config.conv_algo_scope(algo):
                 out, rec = eng._conv3_in(conv, x.to(device), nrm.to(device), 0.01)
