@@ -511,6 +511,46 @@ int64_t mh_overlap_sums_workspace_bytes(int B, int K, int64_t n);
 int mh_overlap_sums(const void* pred, int pred_form, int pred_dtype, const void* truth, int truth_form, int truth_dtype, int B, int K,
                     int64_t n, void* workspace, double* out, void* stream);
 
+/* ---- Surface metrics (HausdorffDistanceMetric / SurfaceDistanceMetric / SurfaceDiceMetric) and the exact EDT -- */
+
+#define MH_ED_BOOL 3 /* a further dtype of a CHANNEL-form side: the stored byte != 0 is foreground (uint8 / float32: value == 1) */
+#define MH_ED_ITEM_WORDS 16
+/* Every kernel below is batched over ITEMS (one per batch element, class and direction): a table of nitems rows of MH_ED_ITEM_WORDS
+ * 64-bit words, given twice -- on the HOST (argument checks, grid sizes) and on the DEVICE (read by the kernels).  Row layout (i = int64,
+ * f = double):  [0] i offset of the item's box in the per-call voxel buffers   [1..3] i box extent d h w (each 1 .. 2048)
+ * [4..6] f spacing z y x   [7] i batch item   [8] i class   [9..11] i box origin z y x in the volume   [12] i offset of the source edge map
+ * [13] i offset of the distance field   [14] f threshold   [15] i offset of the compacted distances.  Boxes of one table do not overlap:
+ * offset + d h w <= total.  A bad row is MH_ERR_ARG before anything is launched. */
+
+/* Union bounding box of prediction | truth per (b, c), c = c0 .. c0 + nc - 1, in place of the CropForegroundd call of get_mask_edges
+ * (monai/metrics/utils.py:200-214).  Sides as in mh_overlap_sums; foreground is value == 1 of a channel (!= 0 for MH_ED_BOOL), label == c of
+ * a label map.  boxes: DEVICE int32[B * nc][8] = z0 y0 x0 d h w has_pred has_truth -- margin 1, clipped to the volume (outside is background
+ * either way), extents 0 without foreground.  Volumes of lower rank pass leading extents of 1. */
+int64_t mh_surface_bbox_workspace_bytes(int B, int nc);
+int mh_surface_bbox(const void* pred, int pred_form, int pred_dtype, const void* truth, int truth_form, int truth_dtype, int B, int K, int c0,
+                    int nc, int D, int H, int W, void* workspace, int32_t* boxes, void* stream);
+/* Edge maps mask & ~binary_erosion(mask) of one side over the items' boxes (rows: 0-3, 7-11), scipy's default element
+ * generate_binary_structure(rank, 1) with border_value = 0 (monai/metrics/utils.py:216-225).  edges: DEVICE uint8[total]. */
+int mh_mask_edges(const void* src, int form, int dtype, int B, int K, int rank, int D, int H, int W, const int64_t* items_host,
+                  const void* items_dev, int nitems, int64_t total, uint8_t* edges, void* stream);
+/* Exact Euclidean distance transform of every item (rows: 0-6) to its nearest FEATURE voxel: a map value != 0, or == 0 with invert
+ * (scipy.ndimage.distance_transform_edt / monai.transforms.utils.distance_transform_edt measure to the nearest ZERO: invert = 1).
+ * map: DEVICE uint8 (map_dtype MH_OV_U8) or float32 (MH_OV_F32) [total].  use_spacing = 0: int32 squared distances, exact; 1: fp64.
+ * The squared field is left at the start of workspace (total elements of int32 / double; the sentinel INT_MAX / +inf where an item has no
+ * feature).  out (may be NULL): distances, sqrt formed in fp64, float32 (out_dtype MH_OV_F32) or float64 (out_dtype 3), +inf without a
+ * feature.  workspace: DEVICE, mh_edt_workspace_bytes(total, use_spacing) bytes (host arithmetic). */
+int64_t mh_edt_workspace_bytes(int64_t total, int use_spacing);
+int mh_edt(const void* map, int map_dtype, int invert, const int64_t* items_host, const void* items_dev, int nitems, int64_t total,
+           int use_spacing, void* workspace, void* out, int out_dtype, void* stream);
+/* Per item (rows: 1-3 with d h w the voxel count, 12-15) over the voxels where edges[src + i] != 0, with f = field[fld + i] and
+ * d = (float)sqrt((double)f) -- get_surface_distance's dis[seg_pred] (monai/metrics/utils.py:242-285) and what the three compute_* functions take
+ * from it: records DEVICE double[nitems][4] = count, max f (-1 without a voxel, +inf for the sentinel), sum of d, count of d <= (float)threshold.
+ * No atomics; the same input gives the same bits.  write = 1 (after a write = 0 call on the same workspace): the d of item k in voxel order at
+ * distances[row 15 ...] (DEVICE float32), records untouched.  workspace: DEVICE, mh_surface_records_workspace_bytes(nitems) bytes. */
+int64_t mh_surface_records_workspace_bytes(int nitems);
+int mh_surface_records(const uint8_t* edges, const void* field, int use_spacing, const int64_t* items_host, const void* items_dev, int nitems,
+                       int64_t total, int write, void* workspace, double* records, float* distances, int64_t ndist, void* stream);
+
 /* ---- Gaussian smoothing (GaussianSmooth / GaussianFilter / separable_filtering) ----------------------------- */
 
 /* dst = src convolved with kz (x) ky (x) kx, zero padding, per channel volume [NC][D][H][W]

@@ -145,6 +145,13 @@ SIGNATURES = {
     "mh_grid_resample_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mh_overlap_sums_workspace_bytes": (_L, [_I, _I, _L]),
     "mh_overlap_sums": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _L, _P, _P, _P]),
+    "mh_surface_bbox_workspace_bytes": (_L, [_I, _I]),
+    "mh_surface_bbox": (_I, [_P, _I, _I, _P, _I, _I] + [_I] * 7 + [_P, _P, _P]),
+    "mh_mask_edges": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _L, _P, _P]),
+    "mh_edt_workspace_bytes": (_L, [_L, _I]),
+    "mh_edt": (_I, [_P, _I, _I, _P, _P, _I, _L, _I, _P, _P, _I, _P]),
+    "mh_surface_records_workspace_bytes": (_L, [_I]),
+    "mh_surface_records": (_I, [_P, _P, _I, _P, _P, _I, _L, _I, _P, _P, _P, _L, _P]),
 }
 
 

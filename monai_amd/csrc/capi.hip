@@ -24,6 +24,7 @@
 #include "kernels/pushpull.h"
 #include "kernels/post.h"
 #include "kernels/metrics.h"
+#include "kernels/edt.h"
 #include "kernels/preproc.h"
 #include "kernels/nn_simple.h"
 #include "kernels/conv1x1_h2.h"
@@ -1748,6 +1749,185 @@ int mh_overlap_sums(const void* pred, int pred_form, int pred_dtype, const void*
     }
 #undef MH_OV_TRUTH
     return launched("overlap_sums");
+}
+
+// ------------------------------------------------------------------------------------------ surface metrics (boxes, edges, exact EDT, surface records)
+static_assert(sizeof(EdItem) == MH_ED_ITEM_WORDS * 8, "item table row");
+
+// (form, dtype) of a side -> 0 channel f32, 1 channel u8, 2 channel bool, 3 labels f32, 4 labels u8, 5 labels i64; -1 with the message set
+static int surf_side(const char* who, const char* side, int form, int dtype) {
+    if (form != OV_CHANNEL && form != OV_LABELS) return fail(MH_ERR_ARG, "%s: unknown form %d of the %s", who, form, side);
+    if (dtype != OV_F32 && dtype != OV_U8 && dtype != OV_I64 && dtype != ED_BOOL) return fail(MH_ERR_ARG, "%s: unknown dtype %d of the %s", who, dtype, side);
+    if (form == OV_CHANNEL && dtype == OV_I64) return fail(MH_ERR_ARG, "%s: a channel-form %s is float32, uint8 or bool, not int64", who, side);
+    if (form == OV_LABELS && dtype == ED_BOOL) return fail(MH_ERR_ARG, "%s: a label-map %s is float32, uint8 or int64, not bool", who, side);
+    return form == OV_CHANNEL ? (dtype == OV_F32 ? 0 : dtype == OV_U8 ? 1 : 2) : (dtype == OV_F32 ? 3 : dtype == OV_U8 ? 4 : 5);
+}
+#define MH_ED_SIDE(kind, CALL)                                          \
+    switch (kind) {                                                     \
+    case 0: { CALL(OV_CHANNEL, float, false); } break;                  \
+    case 1: { CALL(OV_CHANNEL, unsigned char, false); } break;          \
+    case 2: { CALL(OV_CHANNEL, unsigned char, true); } break;           \
+    case 3: { CALL(OV_LABELS, float, false); } break;                   \
+    case 4: { CALL(OV_LABELS, unsigned char, false); } break;           \
+    default: { CALL(OV_LABELS, long long, false); } break;              \
+    }
+
+// rows of a host item table: extents 1 .. 2048 and every box inside [0, total); the largest extents come back for the grids
+static int surf_items_ok(const char* who, const int64_t* items, const void* items_dev, int nitems, int64_t total, int64_t* max_rows, int64_t* max_cols,
+                         int64_t* max_vox) {
+    if (!items || !items_dev) return fail(MH_ERR_ARG, "%s: null item table", who);
+    if (nitems < 1 || nitems > 65535) return fail(MH_ERR_ARG, "%s: %d items (1 .. 65535)", who, nitems);
+    if (total < 1) return fail(MH_ERR_ARG, "%s: bad total %lld", who, (long long)total);
+    *max_rows = *max_cols = *max_vox = 0;
+    for (int k = 0; k < nitems; ++k) {
+        const int64_t* r = items + (int64_t)k * MH_ED_ITEM_WORDS;
+        for (int a = 1; a <= 3; ++a)
+            if (r[a] < 1 || r[a] > ED_MAX_AXIS) return fail(MH_ERR_ARG, "%s: item %d has an extent of %lld (1 .. %d: int32 squared distances)", who, k, (long long)r[a], (int)ED_MAX_AXIS);
+        const int64_t nvox = r[1] * r[2] * r[3];
+        if (r[0] < 0 || r[0] + nvox > total) return fail(MH_ERR_ARG, "%s: item %d leaves the buffers (offset %lld, %lld voxels, total %lld)", who, k, (long long)r[0], (long long)nvox, (long long)total);
+        const int64_t rows = r[1] * r[2], cols = r[1] * r[3] > r[2] * r[3] ? r[1] * r[3] : r[2] * r[3];
+        if (rows > *max_rows) *max_rows = rows;
+        if (cols > *max_cols) *max_cols = cols;
+        if (nvox > *max_vox) *max_vox = nvox;
+    }
+    return MH_OK;
+}
+
+int64_t mh_surface_bbox_workspace_bytes(int B, int nc) {
+    if (B < 1 || nc < 1) return fail(MH_ERR_ARG, "surface_bbox_workspace_bytes: bad argument (B %d, classes %d)", B, nc);
+    return (int64_t)B * nc * 2 * ED_BOX_BLOCKS * 8 * (int64_t)sizeof(int32_t);
+}
+
+int mh_surface_bbox(const void* pred, int pred_form, int pred_dtype, const void* truth, int truth_form, int truth_dtype, int B, int K, int c0, int nc, int D,
+                    int H, int W, void* workspace, int32_t* boxes, void* stream) {
+    if (!pred || !truth || !workspace || !boxes) return fail(MH_ERR_ARG, "surface_bbox: null pointer");
+    if (B < 1 || K < 1 || c0 < 0 || nc < 1 || c0 + nc > K || D < 1 || H < 1 || W < 1)
+        return fail(MH_ERR_ARG, "surface_bbox: bad argument (B %d, K %d, classes %d .. %d, volume %d x %d x %d)", B, K, c0, c0 + nc - 1, D, H, W);
+    if (D > ED_MAX_AXIS || H > ED_MAX_AXIS || W > ED_MAX_AXIS) return fail(MH_ERR_ARG, "surface_bbox: an axis longer than %d (volume %d x %d x %d)", (int)ED_MAX_AXIS, D, H, W);
+    const int kp = surf_side("surface_bbox", "prediction", pred_form, pred_dtype), kt = surf_side("surface_bbox", "truth", truth_form, truth_dtype);
+    if (kp < 0 || kt < 0) return MH_ERR_ARG;
+    if (B > 65535 || nc > 65535) return fail(MH_ERR_UNSUPPORTED, "surface_bbox: problem too large for one launch");
+    const hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(ED_BOX_BLOCKS, (unsigned)nc, (unsigned)B);
+#define MH_ED_BOX(FORM_, T_, BOOL_) hipLaunchKernelGGL((surf_bbox_partial_kernel<FORM_, T_, BOOL_>), grid, dim3(256), 0, st, (const T_*)src, K, c0, D, H, W, side, (int*)workspace)
+    {
+        const void* src = pred;
+        const int side = 0;
+        MH_ED_SIDE(kp, MH_ED_BOX)
+    }
+    {
+        const void* src = truth;
+        const int side = 1;
+        MH_ED_SIDE(kt, MH_ED_BOX)
+    }
+#undef MH_ED_BOX
+    hipLaunchKernelGGL(surf_bbox_final_kernel, dim3((unsigned)(B * nc)), dim3(64), 0, st, (const int*)workspace, (int)ED_BOX_BLOCKS, D, H, W, (int*)boxes);
+    return launched("surface_bbox");
+}
+
+static inline unsigned surf_blocks(int64_t n, int cap) {
+    const int64_t want = (n + 255) / 256;
+    return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
+}
+
+int mh_mask_edges(const void* src, int form, int dtype, int B, int K, int rank, int D, int H, int W, const int64_t* items_host, const void* items_dev, int nitems,
+                  int64_t total, uint8_t* edges, void* stream) {
+    if (!src || !edges) return fail(MH_ERR_ARG, "mask_edges: null pointer");
+    if (B < 1 || K < 1 || rank < 1 || rank > 3 || D < 1 || H < 1 || W < 1 || (rank < 3 && D != 1) || (rank < 2 && H != 1))
+        return fail(MH_ERR_ARG, "mask_edges: bad argument (B %d, K %d, rank %d, volume %d x %d x %d)", B, K, rank, D, H, W);
+    const int kind = surf_side("mask_edges", "mask", form, dtype);
+    if (kind < 0) return MH_ERR_ARG;
+    int64_t mr, mc, mv;
+    if (surf_items_ok("mask_edges", items_host, items_dev, nitems, total, &mr, &mc, &mv) != MH_OK) return MH_ERR_ARG;
+    const int ext[3] = {D, H, W};
+    for (int k = 0; k < nitems; ++k) {
+        const int64_t* r = items_host + (int64_t)k * MH_ED_ITEM_WORDS;
+        if (r[7] < 0 || r[7] >= B || r[8] < 0 || r[8] >= (form == OV_CHANNEL ? K : 2000000000LL)) return fail(MH_ERR_ARG, "mask_edges: item %d names batch item %lld, class %lld", k, (long long)r[7], (long long)r[8]);
+        for (int a = 0; a < 3; ++a)
+            if (r[9 + a] < 0 || r[9 + a] + r[1 + a] > ext[a]) return fail(MH_ERR_ARG, "mask_edges: the box of item %d leaves the volume", k);
+    }
+    const dim3 grid(surf_blocks(mv, 4096), (unsigned)nitems);
+#define MH_ED_EDGE(FORM_, T_, BOOL_) hipLaunchKernelGGL((surf_edge_kernel<FORM_, T_, BOOL_>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)src, K, rank, D, H, W, (const EdItem*)items_dev, edges)
+    MH_ED_SIDE(kind, MH_ED_EDGE)
+#undef MH_ED_EDGE
+    return launched("mask_edges");
+}
+
+int64_t mh_edt_workspace_bytes(int64_t total, int use_spacing) {
+    if (total < 1) return fail(MH_ERR_ARG, "edt_workspace_bytes: bad argument (total %lld)", (long long)total);
+    return total * (2 * (int64_t)(use_spacing ? sizeof(double) : sizeof(int)) + (int64_t)sizeof(unsigned));      // two fields (ping-pong) and the stack
+}
+
+template <typename T, typename V>
+static void edt_launch(const void* map, int invert, const EdItem* items, int nitems, int64_t total, int64_t max_rows, int64_t max_cols, void* workspace, void* out,
+                       int out_dtype, hipStream_t st) {
+    V* fa = (V*)workspace;
+    V* fb = fa + total;
+    unsigned* stack = (unsigned*)(fb + total);
+    hipLaunchKernelGGL((edt_row_kernel<T, V>), dim3((unsigned)((max_rows + 3) / 4), (unsigned)nitems), dim3(256), 0, st, (const T*)map, invert, items, fa);
+    const dim3 cgrid((unsigned)((max_cols + 255) / 256), (unsigned)nitems);
+    hipLaunchKernelGGL((edt_col_kernel<V>), cgrid, dim3(256), 0, st, (const V*)fa, fb, stack, items, 1);
+    hipLaunchKernelGGL((edt_col_kernel<V>), cgrid, dim3(256), 0, st, (const V*)fb, fa, stack, items, 0);
+    if (out) {
+        const dim3 fgrid(surf_blocks(total, 8192));
+        if (out_dtype == OV_F32) hipLaunchKernelGGL((edt_finish_kernel<V, float>), fgrid, dim3(256), 0, st, (const V*)fa, (long long)total, (float*)out);
+        else hipLaunchKernelGGL((edt_finish_kernel<V, double>), fgrid, dim3(256), 0, st, (const V*)fa, (long long)total, (double*)out);
+    }
+}
+
+int mh_edt(const void* map, int map_dtype, int invert, const int64_t* items_host, const void* items_dev, int nitems, int64_t total, int use_spacing, void* workspace,
+           void* out, int out_dtype, void* stream) {
+    if (!map || !workspace) return fail(MH_ERR_ARG, "edt: null pointer");
+    if (map_dtype != OV_F32 && map_dtype != OV_U8) return fail(MH_ERR_ARG, "edt: the map is uint8 or float32 (dtype %d)", map_dtype);
+    if (out && out_dtype != OV_F32 && out_dtype != 3) return fail(MH_ERR_ARG, "edt: distances are float32 (0) or float64 (3), not %d", out_dtype);
+    int64_t mr, mc, mv;
+    if (surf_items_ok("edt", items_host, items_dev, nitems, total, &mr, &mc, &mv) != MH_OK) return MH_ERR_ARG;
+    if (use_spacing) {
+        for (int k = 0; k < nitems; ++k) {
+            double sp[3];
+            memcpy(sp, items_host + (int64_t)k * MH_ED_ITEM_WORDS + 4, sizeof(sp));
+            for (int a = 0; a < 3; ++a)
+                if (!(sp[a] > 0.0) || !(sp[a] < 1e300)) return fail(MH_ERR_ARG, "edt: item %d has a spacing that is not a positive finite number", k);
+        }
+    }
+    if ((mr + 3) / 4 > 0x7fffffffLL) return fail(MH_ERR_UNSUPPORTED, "edt: problem too large for one launch");
+    const hipStream_t st = (hipStream_t)stream;
+    const EdItem* items = (const EdItem*)items_dev;
+    if (map_dtype == OV_U8) {
+        if (use_spacing) edt_launch<unsigned char, double>(map, invert, items, nitems, total, mr, mc, workspace, out, out_dtype, st);
+        else edt_launch<unsigned char, int>(map, invert, items, nitems, total, mr, mc, workspace, out, out_dtype, st);
+    } else {
+        if (use_spacing) edt_launch<float, double>(map, invert, items, nitems, total, mr, mc, workspace, out, out_dtype, st);
+        else edt_launch<float, int>(map, invert, items, nitems, total, mr, mc, workspace, out, out_dtype, st);
+    }
+    return launched("edt");
+}
+
+int64_t mh_surface_records_workspace_bytes(int nitems) {
+    if (nitems < 1) return fail(MH_ERR_ARG, "surface_records_workspace_bytes: bad argument (%d items)", nitems);
+    return (int64_t)nitems * ED_REC_BLOCKS * ED_REC_SLOTS * (int64_t)sizeof(double);
+}
+
+int mh_surface_records(const uint8_t* edges, const void* field, int use_spacing, const int64_t* items_host, const void* items_dev, int nitems, int64_t total, int write,
+                       void* workspace, double* records, float* distances, int64_t ndist, void* stream) {
+    if (!edges || !field || !workspace) return fail(MH_ERR_ARG, "surface_records: null pointer");
+    if (write ? (!distances || ndist < 1) : !records) return fail(MH_ERR_ARG, "surface_records: no output (write %d)", write);
+    int64_t mr, mc, mv;
+    if (surf_items_ok("surface_records", items_host, items_dev, nitems, total, &mr, &mc, &mv) != MH_OK) return MH_ERR_ARG;
+    for (int k = 0; k < nitems; ++k) {
+        const int64_t* r = items_host + (int64_t)k * MH_ED_ITEM_WORDS;
+        const int64_t nvox = r[1] * r[2] * r[3];
+        if (r[12] < 0 || r[12] + nvox > total || r[13] < 0 || r[13] + nvox > total) return fail(MH_ERR_ARG, "surface_records: item %d leaves the buffers", k);
+        if (write && (r[15] < 0 || r[15] > ndist)) return fail(MH_ERR_ARG, "surface_records: item %d writes past the distances", k);
+    }
+    // one piece per block, whole 256-voxel trips: the SAME grid for write = 0 and write = 1 (the pieces' counts place the blocks)
+    const dim3 grid(surf_blocks(mv, ED_REC_BLOCKS), (unsigned)nitems);
+    const hipStream_t st = (hipStream_t)stream;
+    const EdItem* items = (const EdItem*)items_dev;
+    if (use_spacing) hipLaunchKernelGGL(surf_partial_kernel<double>, grid, dim3(256), 0, st, edges, (const double*)field, items, write, (double*)workspace, distances, (long long)ndist);
+    else hipLaunchKernelGGL(surf_partial_kernel<int>, grid, dim3(256), 0, st, edges, (const int*)field, items, write, (double*)workspace, distances, (long long)ndist);
+    if (!write) hipLaunchKernelGGL(surf_final_kernel, dim3((unsigned)nitems), dim3(64), 0, st, (const double*)workspace, (int)grid.x, records);
+    return launched("surface_records");
 }
 
 // ------------------------------------------------------------------------------------------ Gaussian smoothing

@@ -1069,3 +1069,217 @@ def overlap_sums(pred: torch.Tensor, truth: torch.Tensor, num_classes: int) -> t
     L.call("mh_overlap_sums", _lib.ptr(pred), forms[0], _OV_DTYPES[pred.dtype], _lib.ptr(truth), forms[1], _OV_DTYPES[truth.dtype], b, k, n,
            _lib.ptr(ws), _lib.ptr(out), _s(pred))
     return out
+
+
+# ------------------------------------------------------------------------------------------ surface metrics: boxes, edges, exact EDT, surface records
+_ED_DTYPES = {torch.float32: 0, torch.uint8: 1, torch.int64: 2, torch.bool: 3}
+_ED_WORDS = 16
+
+
+class SurfaceRecords:
+    """What `surface_records` leaves on the HOST.  ``present`` bool [B, C, 2]: prediction / truth of (b, c) has any foreground.  ``records`` float64
+    [B, C, 2, 4] for the directions prediction -> truth and truth -> prediction: count of source edge voxels, max squared distance, sum of the float32
+    distances, count of distances <= threshold (zeros where a side is empty or the direction was not asked for).  ``distances[(b, c, direction)]``: the
+    float32 distances in voxel order, when asked for.  ``reads``: device-to-host copies made."""
+
+    def __init__(self, present, records, distances, reads):
+        self.present, self.records, self.distances, self.reads = present, records, distances, reads
+
+
+def _ed_side(t: torch.Tensor, k: int, who: str):
+    if t.shape[1] == k and (k != 1 or t.dtype != torch.int64):
+        if t.dtype == torch.int64:
+            raise _lib.UnsupportedOnDevice(f"monai_amd.{who}: a channel-form tensor is float32, bool or uint8, not int64")
+        return 0, _ED_DTYPES[t.dtype]
+    if t.shape[1] == 1:
+        if t.dtype == torch.bool:
+            raise _lib.UnsupportedOnDevice(f"monai_amd.{who}: a label map is float32, uint8 or int64, not bool")
+        return 1, _ED_DTYPES[t.dtype]
+    raise RuntimeError(f"monai_amd.{who}: a tensor with {t.shape[1]} channels is neither a label map (1) nor one channel per class ({k})")
+
+
+def _ed_volume(t: torch.Tensor, who: str):
+    sp = [int(v) for v in t.shape[2:]]
+    if not 1 <= len(sp) <= 3 or min(sp) < 1:
+        raise NotImplementedError(f"monai_amd.{who}: one to three non-empty spatial axes are what the HIP path takes, got {tuple(t.shape)}")
+    return len(sp), [1] * (3 - len(sp)) + sp
+
+
+def _ed_pair(pred: torch.Tensor, truth: torch.Tensor, num_classes: int, who: str):
+    _lib.require_device(pred, truth, dtypes=tuple(_ED_DTYPES))
+    k = int(num_classes)
+    if pred.dim() < 3 or truth.dim() < 3 or pred.shape[0] != truth.shape[0] or tuple(pred.shape[2:]) != tuple(truth.shape[2:]) or k < 1:
+        raise RuntimeError(f"monai_amd.{who}: [B, C, spatial...] tensors of one batch size and spatial shape required, got {tuple(pred.shape)} and {tuple(truth.shape)}")
+    if not (pred.is_contiguous() and truth.is_contiguous()):
+        raise RuntimeError(f"monai_amd.{who}: contiguous tensors required")
+    rank, vol = _ed_volume(pred, who)
+    return k, rank, vol, _ed_side(pred, k, who), _ed_side(truth, k, who)
+
+
+def _ed_table(rows, device):
+    """rows of (off, d, h, w, (sz, sy, sx), b, c, z0, y0, x0, src_off, fld_off, thr, out_off) -> (host int64 array, the same on the device)"""
+    import numpy as np
+
+    host = np.zeros((len(rows), _ED_WORDS), dtype=np.int64)
+    fl = host.view(np.float64)
+    for i, (off, d, h, w, sp, b, c, z0, y0, x0, so, fo, thr, oo) in enumerate(rows):
+        host[i, 0:4] = (off, d, h, w)
+        fl[i, 4:7] = sp
+        host[i, 7:14] = (b, c, z0, y0, x0, so, fo)
+        fl[i, 14] = thr
+        host[i, 15] = oo
+    return host, torch.from_numpy(host).to(device)
+
+
+def _ed_spacing(sp, rank: int, who: str):
+    import numpy as np
+
+    if sp is None:
+        return (1.0, 1.0, 1.0)
+    if isinstance(sp, (int, float, np.integer, np.floating)):
+        v = [float(sp)] * rank
+    else:
+        v = [float(s) for s in sp]
+        if len(v) != rank:
+            raise RuntimeError(f"monai_amd.{who}: a spacing of {len(v)} values for {rank} spatial axes")
+    return tuple([1.0] * (3 - rank) + v)
+
+
+def surface_boxes(pred: torch.Tensor, truth: torch.Tensor, num_classes: int, first_class: int = 0):
+    """HOST int32 array [B, C, 8] for the classes first_class .. num_classes - 1: z0 y0 x0 d h w of the bounding box of pred | truth (margin 1, clipped to
+    the volume -- the crop of monai/metrics/utils.py:200-214; extents 0 without foreground), has_pred, has_truth.  One device-to-host copy."""
+    k, rank, vol, (pf, pd), (tf, td) = _ed_pair(pred, truth, num_classes, "surface_boxes")
+    b, c0 = int(pred.shape[0]), int(first_class)
+    nc = k - c0
+    if b < 1 or nc < 1:
+        raise RuntimeError(f"monai_amd.surface_boxes: nothing to score (batch {b}, classes {c0} .. {k - 1})")
+    L = _lib.lib()
+    ws = torch.empty(L.query("mh_surface_bbox_workspace_bytes", b, nc), dtype=torch.uint8, device=pred.device)
+    boxes = torch.empty((b, nc, 8), dtype=torch.int32, device=pred.device)
+    L.call("mh_surface_bbox", _lib.ptr(pred), pf, pd, _lib.ptr(truth), tf, td, b, k, c0, nc, vol[0], vol[1], vol[2], _lib.ptr(ws), _lib.ptr(boxes), _s(pred))
+    return boxes.cpu().numpy()
+
+
+def _ed_edges(t: torch.Tensor, side, k: int, rank: int, vol, rows, total: int, edges: torch.Tensor) -> None:
+    host, dev = _ed_table(rows, t.device)
+    _lib.lib().call("mh_mask_edges", _lib.ptr(t), side[0], side[1], int(t.shape[0]), k, rank, vol[0], vol[1], vol[2], host.ctypes.data_as(C.c_void_p), _lib.ptr(dev),
+                    len(rows), total, _lib.ptr(edges), _s(t))
+
+
+def mask_edges(pred: torch.Tensor, truth: torch.Tensor, num_classes: int, first_class: int = 0):
+    """(edges of pred, edges of truth), bool [B, C, spatial...] for the classes first_class .. num_classes - 1: mask & ~binary_erosion(mask) with scipy's
+    default face-connected element and everything outside the volume background (monai/metrics/utils.py:216-225), over the whole volume -- the
+    reference's crop changes no edge voxel.  Each side is a channel form (value == 1, a bool as it is) or a label map (label == c).  No host read."""
+    k, rank, vol, ps, ts = _ed_pair(pred, truth, num_classes, "mask_edges")
+    b, c0 = int(pred.shape[0]), int(first_class)
+    nc, n = k - c0, vol[0] * vol[1] * vol[2]
+    if b < 1 or nc < 1:
+        raise RuntimeError(f"monai_amd.mask_edges: nothing to do (batch {b}, classes {c0} .. {k - 1})")
+    rows = [((bi * nc + ci) * n, vol[0], vol[1], vol[2], (1.0, 1.0, 1.0), bi, c0 + ci, 0, 0, 0, 0, 0, 0.0, 0) for bi in range(b) for ci in range(nc)]
+    out = []
+    for t, side in ((pred, ps), (truth, ts)):
+        e = torch.empty((b, nc) + tuple(pred.shape[2:]), dtype=torch.uint8, device=pred.device)
+        _ed_edges(t, side, k, rank, vol, rows, b * nc * n, e)
+        out.append(e.view(torch.bool))
+    return out[0], out[1]
+
+
+def edt(mask: torch.Tensor, sampling=None, float64: bool = False) -> torch.Tensor:
+    """Exact Euclidean distance of every non-zero voxel of `mask` [C, spatial...] (float32 / uint8 / bool, one to three spatial axes of at most 2048) to
+    the nearest ZERO voxel of its channel, zero at the zeros: scipy.ndimage.distance_transform_edt per channel, as
+    monai.transforms.utils.distance_transform_edt.  float32, or float64 with `float64`; a channel without a zero voxel is +inf everywhere.  Squared
+    distances are exact int32 without `sampling`, fp64 with it; sqrt is formed in fp64 and rounded once.  No host read."""
+    _lib.require_device(mask, dtypes=(torch.float32, torch.uint8, torch.bool))
+    if mask.dim() < 2 or not mask.is_contiguous():
+        raise RuntimeError(f"monai_amd.edt: contiguous [C, spatial...] tensor required, got {tuple(mask.shape)}")
+    rank, vol = _ed_volume(mask.unsqueeze(0), "edt")
+    ch, n = int(mask.shape[0]), vol[0] * vol[1] * vol[2]
+    out = torch.empty(mask.shape, dtype=torch.float64 if float64 else torch.float32, device=mask.device)
+    if ch == 0:
+        return out
+    sp = _ed_spacing(sampling, rank, "edt")
+    host, dev = _ed_table([(i * n, vol[0], vol[1], vol[2], sp, 0, i, 0, 0, 0, 0, 0, 0.0, 0) for i in range(ch)], mask.device)
+    L = _lib.lib()
+    use_sp = int(sampling is not None)
+    ws = torch.empty(L.query("mh_edt_workspace_bytes", ch * n, use_sp), dtype=torch.uint8, device=mask.device)
+    L.call("mh_edt", _lib.ptr(mask), 0 if mask.dtype == torch.float32 else 1, 1, host.ctypes.data_as(C.c_void_p), _lib.ptr(dev), ch, ch * n, use_sp, _lib.ptr(ws),
+           _lib.ptr(out), 3 if float64 else 0, _s(mask))
+    return out
+
+
+def surface_records(pred: torch.Tensor, truth: torch.Tensor, num_classes: int, spacing=None, thresholds=None, symmetric: bool = True, first_class: int = 0,
+                    want_distances: bool = False) -> SurfaceRecords:
+    """The surface-distance record of every (batch item, class first_class .. num_classes - 1) that HausdorffDistanceMetric, SurfaceDistanceMetric and
+    SurfaceDiceMetric are finished from (csrc/kernels/edt.h; monai/metrics/utils.py:139-344).  pred / truth [B, C, spatial...]: each side on its own a channel
+    form (C == num_classes; value == 1 is foreground, a bool as it is) or a label map (C == 1).  `spacing`: None or one entry per batch item (None, a
+    number or one number per axis); `thresholds`: one per scored class; `symmetric`: also truth -> prediction.
+
+    Launches are batched over (b, c, direction); device-to-host copies per call: the boxes, the records and -- with `want_distances` -- the compacted
+    distances: three at most, whatever the voxel count, B or the number of classes."""
+    import numpy as np
+
+    k, rank, vol, ps, ts = _ed_pair(pred, truth, num_classes, "surface_records")
+    b, c0 = int(pred.shape[0]), int(first_class)
+    nc = k - c0
+    if spacing is not None and len(spacing) != b:
+        raise RuntimeError(f"monai_amd.surface_records: {len(spacing)} spacings for a batch of {b}")
+    if thresholds is not None and len(thresholds) != nc:
+        raise RuntimeError(f"monai_amd.surface_records: {len(thresholds)} thresholds for {nc} classes")
+    boxes = surface_boxes(pred, truth, k, c0)
+    present = torch.from_numpy(boxes[:, :, 6:8] != 0)
+    records = torch.zeros((b, nc, 2, 4), dtype=torch.float64)
+    distances: dict = {}
+    reads = 1
+    use_sp = int(spacing is not None and any(s is not None for s in spacing))
+    pairs = [(bi, ci) for bi in range(b) for ci in range(nc) if boxes[bi, ci, 6] and boxes[bi, ci, 7]]
+    if not pairs:
+        return SurfaceRecords(present, records, distances, reads)
+    dev = pred.device
+    e_rows_p, e_rows_t, f_rows, r_rows, r_keys = [], [], [], [], []
+    total = 0
+    for bi, ci in pairs:
+        z0, y0, x0, d, h, w = (int(v) for v in boxes[bi, ci, :6])
+        nvox = d * h * w
+        sp = _ed_spacing(spacing[bi] if spacing is not None else None, rank, "surface_records")
+        thr = float(np.float32(thresholds[ci])) if thresholds is not None else 0.0
+        op, ot = total, total + nvox
+        total += 2 * nvox
+        e_rows_p.append((op, d, h, w, sp, bi, c0 + ci, z0, y0, x0, 0, 0, 0.0, 0))
+        e_rows_t.append((ot, d, h, w, sp, bi, c0 + ci, z0, y0, x0, 0, 0, 0.0, 0))
+        f_rows.append(e_rows_t[-1])
+        r_rows.append((op, d, h, w, sp, bi, c0 + ci, z0, y0, x0, op, ot, thr, 0))
+        r_keys.append((bi, ci, 0))
+        if symmetric:
+            f_rows.append(e_rows_p[-1])
+            r_rows.append((ot, d, h, w, sp, bi, c0 + ci, z0, y0, x0, ot, op, thr, 0))
+            r_keys.append((bi, ci, 1))
+    L = _lib.lib()
+    edges = torch.empty(total, dtype=torch.uint8, device=dev)
+    _ed_edges(pred, ps, k, rank, vol, e_rows_p, total, edges)
+    _ed_edges(truth, ts, k, rank, vol, e_rows_t, total, edges)
+    ws = torch.empty(L.query("mh_edt_workspace_bytes", total, use_sp), dtype=torch.uint8, device=dev)
+    f_host, f_dev = _ed_table(f_rows, dev)
+    L.call("mh_edt", _lib.ptr(edges), 1, 0, f_host.ctypes.data_as(C.c_void_p), _lib.ptr(f_dev), len(f_rows), total, use_sp, _lib.ptr(ws), None, 0, _s(pred))
+    r_host, r_dev = _ed_table(r_rows, dev)
+    rws = torch.empty(L.query("mh_surface_records_workspace_bytes", len(r_rows)), dtype=torch.uint8, device=dev)
+    rec = torch.empty((len(r_rows), 4), dtype=torch.float64, device=dev)
+    L.call("mh_surface_records", _lib.ptr(edges), _lib.ptr(ws), use_sp, r_host.ctypes.data_as(C.c_void_p), _lib.ptr(r_dev), len(r_rows), total, 0, _lib.ptr(rws),
+           _lib.ptr(rec), None, 0, _s(pred))
+    rec_h = rec.cpu()
+    reads += 1
+    for i, key in enumerate(r_keys):
+        records[key] = rec_h[i]
+    if want_distances:
+        counts = [int(v) for v in rec_h[:, 0].tolist()]
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        r_rows = [row[:13] + (int(offs[i]),) for i, row in enumerate(r_rows)]
+        r_host, r_dev = _ed_table(r_rows, dev)
+        nd = int(offs[-1])
+        dist = torch.empty(max(nd, 1), dtype=torch.float32, device=dev)
+        L.call("mh_surface_records", _lib.ptr(edges), _lib.ptr(ws), use_sp, r_host.ctypes.data_as(C.c_void_p), _lib.ptr(r_dev), len(r_rows), total, 1, _lib.ptr(rws),
+               None, _lib.ptr(dist), max(nd, 1), _s(pred))
+        dist_h = dist.cpu()
+        reads += 1
+        for i, key in enumerate(r_keys):
+            distances[key] = dist_h[int(offs[i]):int(offs[i + 1])]
+    return SurfaceRecords(present, records, distances, reads)

@@ -81,6 +81,7 @@ _TARGETS = {
     "monai.transforms.post.array": {
         "Activations": ("monai_amd.transforms.post.array", "Activations"),
         "AsDiscrete": ("monai_amd.transforms.post.array", "AsDiscrete"),
+        "DistanceTransformEDT": ("monai_amd.transforms.post.array", "DistanceTransformEDT"),
     },
     "monai.transforms.post.dictionary": {
         "Activationsd": ("monai_amd.transforms.post.dictionary", "Activationsd"),
@@ -89,6 +90,9 @@ _TARGETS = {
         "AsDiscreted": ("monai_amd.transforms.post.dictionary", "AsDiscreted"),
         "AsDiscreteD": ("monai_amd.transforms.post.dictionary", "AsDiscreted"),
         "AsDiscreteDict": ("monai_amd.transforms.post.dictionary", "AsDiscreted"),
+        "DistanceTransformEDTd": ("monai_amd.transforms.post.dictionary", "DistanceTransformEDTd"),
+        "DistanceTransformEDTD": ("monai_amd.transforms.post.dictionary", "DistanceTransformEDTd"),
+        "DistanceTransformEDTDict": ("monai_amd.transforms.post.dictionary", "DistanceTransformEDTd"),
     },
     "monai.transforms.intensity.dictionary": {
         "GaussianSmoothd": ("monai_amd.transforms.intensity.dictionary", "GaussianSmoothd"),
@@ -117,7 +121,13 @@ _TARGETS = {
     "monai.metrics.meaniou": {n: ("monai_amd.metrics.meaniou", n) for n in ("MeanIoU", "compute_iou")},
     "monai.metrics.confusion_matrix": {n: ("monai_amd.metrics.confusion_matrix", n) for n in
                                        ("ConfusionMatrixMetric", "get_confusion_matrix", "compute_confusion_matrix_metric", "check_confusion_matrix_metric_name")},
-    "monai.metrics.utils": {n: ("monai_amd.metrics.utils", n) for n in ("do_metric_reduction", "ignore_background", "is_binary_tensor")},
+    "monai.metrics.utils": {n: ("monai_amd.metrics.utils", n) for n in
+                            ("do_metric_reduction", "ignore_background", "is_binary_tensor", "get_mask_edges", "get_surface_distance", "get_edge_surface_distance",
+                             "prepare_spacing")},
+    "monai.metrics.hausdorff_distance": {n: ("monai_amd.metrics.hausdorff_distance", n) for n in ("HausdorffDistanceMetric", "compute_hausdorff_distance")},
+    "monai.metrics.surface_distance": {n: ("monai_amd.metrics.surface_distance", n) for n in ("SurfaceDistanceMetric", "compute_average_surface_distance")},
+    "monai.metrics.surface_dice": {n: ("monai_amd.metrics.surface_dice", n) for n in ("SurfaceDiceMetric", "compute_surface_dice")},
+    "monai.transforms.utils": {"distance_transform_edt": ("monai_amd.transforms.utils", "distance_transform_edt")},
 }
 # parent packages that re-export the names above
 _REEXPORT = ["monai.inferers", "monai.networks.nets", "monai.transforms", "monai.networks.layers", "monai.networks.blocks", "monai.metrics"]

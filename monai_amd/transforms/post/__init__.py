@@ -1,2 +1,4 @@
-from .array import Activations, AsDiscrete  # noqa: F401
-from .dictionary import ActivationsD, ActivationsDict, Activationsd, AsDiscreteD, AsDiscreteDict, AsDiscreted  # noqa: F401
+from .array import Activations, AsDiscrete, DistanceTransformEDT  # noqa: F401
+from .dictionary import (  # noqa: F401
+    ActivationsD, ActivationsDict, Activationsd, AsDiscreteD, AsDiscreteDict, AsDiscreted, DistanceTransformEDTD, DistanceTransformEDTDict, DistanceTransformEDTd,
+)

@@ -12,7 +12,7 @@ import torch
 from ... import ops
 from ...utils.misc import look_up_option
 
-__all__ = ["Activations", "AsDiscrete"]
+__all__ = ["Activations", "AsDiscrete", "DistanceTransformEDT"]
 
 
 def _is_meta(x) -> bool:
@@ -94,3 +94,16 @@ class AsDiscrete:
             look_up_option(rounding, ["torchrounding"])
             t = ops.pointwise("round", t)
         return _like(t, img)
+
+
+class DistanceTransformEDT:
+    """Exact Euclidean distance transform of a channel-first image, channel by channel (monai/transforms/post/array.py:996-1029): float32 distances to
+    the nearest zero voxel, ``+inf`` in a channel without one (see `monai_amd.transforms.utils.distance_transform_edt`)."""
+
+    def __init__(self, sampling=None) -> None:
+        self.sampling = sampling
+
+    def __call__(self, img):
+        from ..utils import distance_transform_edt
+
+        return distance_transform_edt(img=img, sampling=self.sampling)

@@ -9,9 +9,10 @@ from __future__ import annotations
 from collections.abc import Callable, Hashable, Mapping, Sequence
 
 from ...utils.misc import ensure_tuple, ensure_tuple_rep
-from .array import Activations, AsDiscrete
+from .array import Activations, AsDiscrete, DistanceTransformEDT
 
-__all__ = ["Activationsd", "ActivationsD", "ActivationsDict", "AsDiscreted", "AsDiscreteD", "AsDiscreteDict"]
+__all__ = ["Activationsd", "ActivationsD", "ActivationsDict", "AsDiscreted", "AsDiscreteD", "AsDiscreteDict", "DistanceTransformEDTd", "DistanceTransformEDTD",
+           "DistanceTransformEDTDict"]
 
 
 class _PerKey:
@@ -69,5 +70,17 @@ class AsDiscreted(_PerKey):
         self._bind(keys, allow_missing_keys, kwargs, argmax=argmax, to_onehot=to_onehot, threshold=threshold, rounding=rounding)
 
 
+class DistanceTransformEDTd(_PerKey):
+    """monai/transforms/post/dictionary.py:871-913"""
+
+    array_transform = DistanceTransformEDT
+
+    def __init__(self, keys, allow_missing_keys: bool = False, sampling=None) -> None:
+        self._bind(keys, allow_missing_keys, {})
+        self.sampling = sampling
+        self.distance_transform = self.converter = DistanceTransformEDT(sampling=sampling)
+
+
 ActivationsD = ActivationsDict = Activationsd
+DistanceTransformEDTD = DistanceTransformEDTDict = DistanceTransformEDTd
 AsDiscreteD = AsDiscreteDict = AsDiscreted
