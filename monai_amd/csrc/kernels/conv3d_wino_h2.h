@@ -14,8 +14,12 @@
 // tile's 4 x 4 patch that its positions need (row i of B^T d B: i = 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3 -- wave-uniform (row, row, sign); the columns likewise),
 // forms its two V[i][j] in packed fp32 and splits each into hi / lo fp16 (the split comes AFTER the transform: the sums are exact to fp32 rounding); (3) 36 matrix
 // instructions: for both positions, every z-tap t and cout block  acc[plane p + 1 - t] += Vh Uh + Vl Uh + Vh Ul;  (4) when output plane p - 1 is complete the wave's two
-// terms of the inverse transform's column half go to LDS (no register shuffling: s = M_a + M_b and M_b as plain 16-byte items), and two iterations later every wave
-// finishes a quarter of a row pair  Y[a'][b'] = sum_i A^T[a'][i] Z[i][b']  from 8-byte reads (scale back, bias, statistics as shifted sums, one 16-byte store per row).
+// terms of the inverse transform's column half go to LDS (no register shuffling: s = M_a + M_b and M_b as plain 16-byte items; the items of tile columns 4-7 at cout ^ 12,
+// chosen by the bank rule of the ds_read2st64_b64 the reads below compile to: see zwr / zrd), and two iterations later every wave finishes two of the region's four output rows for 8 couts:
+// Y[a'][b'] = sum_i A^T[a'][i] Z[i][b']  from 8-byte reads (scale back, bias, statistics as shifted sums, one 16-byte store per lane).  The finishing lanes are laid out
+// ALONG THE ROW: the four lanes of an aligned quad hold the four 16-byte pieces of one 64-byte row of one cout, so a store instruction of the wave is 16 whole 64-byte
+// segments -- the L1 sends one write request per segment a wave instruction touches, and with a cout per lane (the matrix instruction's own layout) that was 64 requests
+// of 16 bytes: 453 M of the launch's 784 M L2 requests at 96^3 x 64 windows (profiles/r06_pmc_h2w_mem.txt).
 // An iteration is two barrier-separated phases -- transform | matrix instructions + staging + finishing + Z items -- and the jp = 1 waves run one phase behind the jp = 0
 // waves, so the two waves of a SIMD are never in the same kind of phase.  The accumulator sets rotate by NAME (the march is unrolled three times); a fresh set starts from
 // the instruction's zero C operand.  ACC: out += ... (old values requested at the start of the iteration's vector phase); POOL: MaxPool3d(2) of the result leaves with it
@@ -40,7 +44,7 @@ constexpr int HWG_RY = HWG_BY + 2, HWG_RX = HWG_BX + 2;     // staged rows, colu
 constexpr int HWG_NP = HWG_RY * HWG_RX;                     // staged positions (108)
 constexpr int HWG_PB = 144;                                 // bytes per position: 32 channels fp32 + 16 (bank spread)
 constexpr int HWG_DB = (HWG_NP + 1) * HWG_PB;               // bytes per input buffer (one dump position at the end): 15 696
-constexpr int HWG_ZB = 32 * 1024;                           // bytes per Z exchange buffer: [8 waves = 2 column halves x 4 rows i][2 blocks][2 register pairs][64 lanes][16 bytes]
+constexpr int HWG_ZB = 32 * 1024;                           // bytes per Z exchange buffer: [8 waves = 2 column halves x 4 rows i][2 blocks][s | a1][64 items][16 bytes]
 constexpr int HWG_OPS = 24;                                 // B operands per wave: [slot][t][cout block][piece]
 constexpr int HWG_CIN = 32, HWG_CN = 32;
 constexpr int HWG_WAVES = 8;                                // waves of a workgroup
@@ -102,6 +106,20 @@ __device__ __forceinline__ float hw_xchg32(const float x, const int hi) {
 #else
 #define MH_HW_KEEP_BRANCH asm volatile("" ::: "memory")
 #endif
+
+// The finishing role of a lane (see "finishing role" in the kernel): cout within the group, output row a' of the tile, D-row group, register pair, quarter of the row
+struct HwFinish {
+    int co_l, fa, g4, frp, fq;
+};
+__device__ __forceinline__ HwFinish hw_finish_role(const int wave, const int lane) {
+    HwFinish r;
+    r.fq = lane & 3;
+    r.frp = r.fq & 1;
+    r.fa = lane >> 5;
+    r.g4 = ((wave >> 1) & 1) ? (r.fq >> 1 ? 2 : 1) : (r.fq >> 1 ? 3 : 0);
+    r.co_l = (wave >> 2) * 16 + (wave & 1) * 8 + ((lane >> 2) & 7);
+    return r;
+}
 
 template <bool STATS, bool ACC = false, bool POOL = false>
 __global__ void __launch_bounds__(512)
@@ -237,20 +255,31 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
 #pragma unroll
             for (int c = 0; c < 2; ++c) acc[s][j][c] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
-    // ---- finishing role: wave = (cout block fcb, register pair frp, half fh of the 64 items); lanes 0-31 finish output row a' = 0 of items 32 fh + (lane & 31),
-    // lanes 32-63 row a' = 1 of the same items (the 2 x 2 pooling window of a tile is then the lane pair l, l ^ 32) ---------------------------------------------
-    const int fcb = wave >> 2, frp = (wave >> 1) & 1, fh = wave & 1;
-    const int il = 32 * fh + (lane & 31), fa = lane >> 5;
-    const int g4 = il >> 4;                                    // D rows 4 g4 + r  ->  g4 0: ty 0, tx 0-3; 1: ty 1, tx 0-3; 2: ty 1, tx 4-7; 3: ty 0, tx 4-7
-    const int fty = (g4 == 1 || g4 == 2) ? 1 : 0, ftx = (g4 >= 2 ? 4 : 0) + 2 * frp;
-    const int co_l = fcb * 16 + (il & 15), co = cg * HWG_CN + co_l;
+    // ---- finishing role: wave = (cout block fcb, tile row fty, half fch of the block's 16 couts); lane = (output row a' = fa = lane >> 5, cout 8 fch + ((lane >> 2) & 7),
+    // quarter fq = lane & 3 of the region's row).  The four lanes of an aligned quad hold the four 16-byte pieces x0 + 4 fq .. + 3 of ONE 64-byte row of one cout, in
+    // ascending order: a store (and an old-value load of the accumulating form) of the wave is 16 whole 64-byte segments, a pooled store 16 runs of 32 bytes, instead of
+    // 64 pieces that the L1 hands to the L2 one request each.  Lanes l and l ^ 32 finish rows a' = 0 and 1 of the same tiles (the 2 x 2 pooling window of a tile is the
+    // lane pair).  A piece is the register pair frp = fq & 1 of the item of D-row group g4 (D rows 4 g4 + r  ->  g4 0: ty 0, tx 0-3; 1: ty 1, tx 0-3; 2: ty 1, tx 4-7;
+    // 3: ty 0, tx 4-7): which lane finishes it does not change what it holds ----------------------------------------------------------------------------------
+    const HwFinish fr = hw_finish_role(wave, lane);
+    const int fcb = wave >> 2, fty = (wave >> 1) & 1;
+    const int fa = fr.fa, fq = fr.fq, frp = fr.frp, g4 = fr.g4;
+    const int ftx = 2 * fq;                                    // = (g4 >= 2 ? 4 : 0) + 2 frp
+    const int c16 = fr.co_l & 15;
+    const int co_l = fr.co_l, co = cg * HWG_CN + co_l;
     const float bco = bias ? bias[co] : 0.0f;
     const float fs2 = fa ? -1.0f : 1.0f;
     // Z exchange: wave w = jp 4 + i leaves, per cout block, s = slot 0 + slot 1 and a1 = slot 1 of its completed set as two 16-byte items per lane (no register
-    // shuffling): [parity][wave][cout block][s | a1][lane][4 tile rows].  With (M0, M1) in the jp 0 wave and (M3, M2) in the jp 1 wave of row i:
-    // Z[b' = 0] = M0 + M1 + M2 = s(jp 0) + a1(jp 1),  Z[b' = 1] = M1 - M2 - M3 = a1(jp 0) - s(jp 1).  The finishing lane reads the register pair frp of its item.
-    const int zwr = wave * 4096 + lane * 16;
-    const int zrd = fa * 4096 + fcb * 2048 + il * 16 + frp * 8;         // row i0 = a' of the jp 0 half (jp 1: + 16384; row + 1: + 4096; a1: + 1024)
+    // shuffling): [parity][wave][cout block][s | a1][item = g4 16 + (cout ^ (g4 >= 2 ? 12 : 0))][4 tile rows].  With (M0, M1) in the jp 0 wave and (M3, M2) in the jp 1
+    // wave of row i:  Z[b' = 0] = M0 + M1 + M2 = s(jp 0) + a1(jp 1),  Z[b' = 1] = M1 - M2 - M3 = a1(jp 0) - s(jp 1).  The finishing lane reads the register pair frp
+    // of its item.  Why the items of g4 = 2, 3 sit at cout ^ 12: the reads' compile-time offsets (+ 1024, + 4096, + 16384) are multiples of 512, so hipcc pairs them
+    // into ds_read2st64_b64, whose accesses are banked (a / 4) mod 32 -- a 128-byte row -- per group of 16 contiguous lanes.  A group is 4 couts x 4 quarters; fq < 2
+    // reads (cout mod 8) 16 + frp 8 of its row, fq >= 2 reads ((cout ^ 4) mod 8) 16 + frp 8: the other 64 bytes -- 16 different 8-byte slots.  (Un-swizzled, and with
+    // cout ^ 8, both land on the same 64 bytes: two lanes per bank.)  Were the reads left as single ds_read_b64 -- 32-lane halves over a 256-byte row -- bit 3 of the
+    // XOR puts the two g4 of a half wave on opposite 128-byte halves: 32 different slots.  The 16-byte writes are banked mod 32 per 8 contiguous lanes: an aligned group
+    // still writes one contiguous, aligned 128 bytes, its two 64-byte halves exchanged.
+    const int zwr = wave * 4096 + (lane ^ ((lane >> 5) * 12)) * 16;       // lanes 32-63 (g4 = 2, 3): cout ^ 12
+    const int zrd = fa * 4096 + fcb * 2048 + (g4 * 16 + (c16 ^ (fq >> 1 ? 12 : 0))) * 16 + frp * 8;         // row i0 = a' of the jp 0 half (jp 1: + 16384; row + 1: + 4096; a1: + 1024)
     float inv_a, inv_b;
     {
         const int t_ = -((int)((__float_as_uint(wtail[1]) >> 23) & 0xffu) - 127) - e_in;      // wtail[1] = the weights' power-of-two scale
@@ -457,26 +486,33 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
             run.mean = pivot + dm;
             run.m2 = fmaxf(a2 - a1 * dm, 0.0f);
         }
-        // a cout's voxels sit in the four lane groups 16 apart of the lower half, the two rows (lane ^ 32) and the four waves that share its cout block
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-            Stat ot;
-            ot.n = __shfl_xor(run.n, o); ot.mean = __shfl_xor(run.mean, o); ot.m2 = __shfl_xor(run.m2, o);
-            run = (lane & o) == 0 ? stat_merge(run, ot) : stat_merge(ot, run);
-        }
+        // a cout's 16 leaves (a', g4, frp) sit in eight lanes of two waves.  The records are merged in ONE fixed tree, whatever lane finished which piece (the
+        // records of a launch are the same bits under every finishing role): per (frp, pair of g4)  merge(merge(g4 even, g4 odd) of a' = 0, the same of a' = 1),
+        // then a left fold from the zero record over (frp, pair) = (0, 0), (0, 1), (1, 0), (1, 1).  Once per workgroup: all 512 leaves to LDS, one thread per cout.
         __syncthreads();
         float* red = reinterpret_cast<float*>(smem);
-        if (lane < 16) { red[(wave * 16 + lane) * 3] = run.n; red[(wave * 16 + lane) * 3 + 1] = run.mean; red[(wave * 16 + lane) * 3 + 2] = run.m2; }
+        {
+            int t_ = tid;
+            MH_OPAQUE(t_);      // the role once more from the thread index: nothing of it is held in a register over the march for this
+            const HwFinish e = hw_finish_role(t_ >> 6, t_ & 63);
+            float* leaf = red + (((e.co_l * 2 + e.fa) * 4 + e.g4) * 2 + e.frp) * 3;
+            leaf[0] = run.n; leaf[1] = run.mean; leaf[2] = run.m2;
+        }
         __syncthreads();
         if (tid < HWG_CN) {
-            const int cb = tid >> 4, c16 = tid & 15;
+            const auto leaf_of = [&](int a, int g, int rp) {
+                const float* l = red + (((tid * 2 + a) * 4 + g) * 2 + rp) * 3;
+                Stat s;
+                s.n = l[0]; s.mean = l[1]; s.m2 = l[2];
+                return s;
+            };
             Stat st;
             st.n = 0.0f; st.mean = 0.0f; st.m2 = 0.0f;
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
-                Stat ot;
-                ot.n = red[((4 * cb + w) * 16 + c16) * 3]; ot.mean = red[((4 * cb + w) * 16 + c16) * 3 + 1]; ot.m2 = red[((4 * cb + w) * 16 + c16) * 3 + 2];
-                st = stat_merge(st, ot);
+                const int rp = w >> 1, ge = 2 * (w & 1);
+                const Stat r0 = stat_merge(leaf_of(0, ge, rp), leaf_of(0, ge + 1, rp)), r1 = stat_merge(leaf_of(1, ge, rp), leaf_of(1, ge + 1, rp));
+                st = stat_merge(st, stat_merge(r0, r1));
             }
             float* rec = stats + (((long long)n * Cout + cg * HWG_CN + tid) * nblk + b) * 3;
             rec[0] = st.n; rec[1] = st.mean; rec[2] = st.m2;
