@@ -551,6 +551,55 @@ int64_t mh_surface_records_workspace_bytes(int nitems);
 int mh_surface_records(const uint8_t* edges, const void* field, int use_spacing, const int64_t* items_host, const void* items_dev, int nitems,
                        int64_t total, int write, void* workspace, double* records, float* distances, int64_t ndist, void* stream);
 
+/* ---- connected components (KeepLargestConnectedComponent, FillHoles, LabelFilter) --------------------------- */
+
+/* The labelling primitive of get_largest_connected_component_mask (monai/transforms/utils.py:1134-1180: skimage.measure.label on the host, cuCIM +
+ * CuPy on a CUDA device) and of fill_holes (transforms/utils.py:1504-1560: scipy's iterated binary_dilation from the border on the host), and the
+ * kernels KeepLargestConnectedComponent, FillHoles and LabelFilter (monai/transforms/post/array.py:239-354, 503-578, 445-500) apply them with.
+ * dtype codes: MH_OV_F32 0, MH_OV_U8 1, MH_OV_I64 2, bool 3 (one byte).  Everything is batched over ITEMS: a table of nitems rows of MH_CC_ITEM_WORDS
+ * 64-bit words, once on the HOST (checked before anything is launched) and once on the DEVICE (read by the kernels):
+ *   0 off: voxel offset of the item in the label / record buffers     1 src: element offset of the item's volume in the tensor
+ *   2-4 d h w: extent, d = 1 at rank 2; at most MH_CC_MAX_VOXELS voxels, any axis length
+ *   5 rule: class id of a voxel, 0 = background: MH_CC_GT value > 0, MH_CC_EQ value == v, MH_CC_NE value != v (one class each),
+ *     MH_CC_LIST_VALUE 1 + the position of the value in the list (one class per listed value: every class of a label map in one pass),
+ *     MH_CC_LIST_ANY 1 if the value is in the list, MH_CC_VALUE the value itself (every non-zero value its own class, as skimage.measure.label
+ *     reads an integer image).  Rows of one table may use different rules.        6 number of listed labels (0 .. 32)        7 v (double)
+ *   8 fill value (double), 9 fill mode (mh_cc_fill)        10-15 unused        16-47 the listed labels (double, distinct)
+ * No entry needs a workspace, allocates or synchronises. */
+#define MH_CC_ITEM_WORDS 48
+#define MH_CC_MAX_VOXELS 2147483646LL
+#define MH_CC_MAX_KEEP 1024
+#define MH_CC_GT 0
+#define MH_CC_EQ 1
+#define MH_CC_NE 2
+#define MH_CC_LIST_VALUE 3
+#define MH_CC_LIST_ANY 4
+#define MH_CC_VALUE 5
+#define MH_CC_FILL_VALUE 0
+#define MH_CC_FILL_BINARY 1
+/* labels (DEVICE int32[total]): 0 for background, otherwise 1 + the linear index inside the item (C order) of the first voxel of the component --
+ * the same bits on every run.  Two voxels are connected if they have the same non-zero class id and lie within `connectivity` orthogonal hops
+ * (1 .. rank; rank 2 or 3), as skimage.measure.label(connectivity=) and scipy.ndimage.generate_binary_structure(rank, connectivity) define it.
+ * src: DEVICE tensor of src_elems elements.  Union-find over row runs; link words are lowered with integer atomic minima. */
+int mh_cc_label(const void* src, int dtype, int64_t src_elems, int rank, int connectivity, const int64_t* items_host, const void* items_dev, int nitems,
+                int64_t total, int32_t* labels, void* stream);
+/* Component records at ROOT positions (sizes[off + label - 1], border[off + label - 1]; zero elsewhere inside every item): the voxel count
+ * (numpy.bincount of the label image, as get_largest_connected_component_mask ranks components) and whether any voxel of the component has a
+ * coordinate 0 or extent - 1 along one of the item's `rank` axes (such a component of the background is open in fill_holes).  rows: 0, 2-4. */
+int mh_cc_records(const int32_t* labels, int rank, const int64_t* items_host, const void* items_dev, int nitems, int64_t total, int32_t* sizes,
+                  uint8_t* border, void* stream);
+/* data[src + i] = 0 for every voxel of an item with labels[off + i] > 0 that is not one of keep[item][0 .. nkeep) (DEVICE int32, entries <= 0
+ * are padding): `img_[foreground != mask] = 0` of KeepLargestConnectedComponent.  rows: 0-4. */
+int mh_cc_keep(void* data, int dtype, int64_t data_elems, const int32_t* labels, const int32_t* keep, int nkeep, int rank, const int64_t* items_host,
+               const void* items_dev, int nitems, int64_t total, void* stream);
+/* Per item, with "enclosed" = labels[off + i] > 0 and the component's border flag 0: MH_CC_FILL_VALUE writes the fill value into the enclosed
+ * voxels (`img_arr[0, logical_not(tmp)] = label` of fill_holes); MH_CC_FILL_BINARY rewrites the volume as 1 where labels == 0 or enclosed, 0
+ * elsewhere (`img_arr[label] = logical_not(tmp)`).  rows: 0-4, 8, 9. */
+int mh_cc_fill(void* data, int dtype, int64_t data_elems, const int32_t* labels, const uint8_t* border, int rank, const int64_t* items_host,
+               const void* items_dev, int nitems, int64_t total, void* stream);
+/* dst[i] = src[i] if it equals one of labels[0 .. nlabels) (HOST doubles, at most 32), else 0: LabelFilter. */
+int mh_cc_filter(const void* src, void* dst, int dtype, int64_t n, const double* labels, int nlabels, void* stream);
+
 /* ---- Gaussian smoothing (GaussianSmooth / GaussianFilter / separable_filtering) ----------------------------- */
 
 /* dst = src convolved with kz (x) ky (x) kx, zero padding, per channel volume [NC][D][H][W]

@@ -163,6 +163,18 @@ def _dict_in(obj, args, kwargs):
     return ((d,) + tuple(args[1:]), kwargs) if changed else (args, kwargs)
 
 
+def _numpy_to_reference(obj, args) -> None:
+    """transforms whose reference returns a numpy array for a numpy array (``_mh_numpy_to_reference``, e.g. LabelFilter): such a call is the reference's"""
+    import numpy as np
+
+    if not getattr(obj, "_mh_numpy_to_reference", False) or not args:
+        return
+    x = args[0]
+    vals = [x[k] for k in getattr(obj, "keys", ()) if k in x] if isinstance(x, dict) else [x]
+    if any(isinstance(v, np.ndarray) for v in vals):
+        raise NotImplementedError(f"monai_amd.{type(obj).__name__}: a numpy array in, a numpy array out is the reference's path")
+
+
 def _dict_out(obj, out):
     if isinstance(out, dict):
         for k in getattr(obj, "keys", ()) or ():
@@ -344,6 +356,8 @@ def reference_fallback(ref_module: str, name: str, methods=("__call__",), share_
                         if out is not args[0] and len(ops_) == n_before and n_before > 0:
                             ops_.pop()
                         return out
+                    if mname == "__call__":
+                        _numpy_to_reference(self, args)
                     if image_io and mname == "__call__":
                         a2, k2 = _image_in(args, kwargs)
                         out = _image_out(orig(self, *a2, **k2))

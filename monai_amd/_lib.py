@@ -152,6 +152,11 @@ SIGNATURES = {
     "mh_edt": (_I, [_P, _I, _I, _P, _P, _I, _L, _I, _P, _P, _I, _P]),
     "mh_surface_records_workspace_bytes": (_L, [_I]),
     "mh_surface_records": (_I, [_P, _P, _I, _P, _P, _I, _L, _I, _P, _P, _P, _L, _P]),
+    "mh_cc_label": (_I, [_P, _I, _L, _I, _I, _P, _P, _I, _L, _P, _P]),
+    "mh_cc_records": (_I, [_P, _I, _P, _P, _I, _L, _P, _P, _P]),
+    "mh_cc_keep": (_I, [_P, _I, _L, _P, _P, _I, _I, _P, _P, _I, _L, _P]),
+    "mh_cc_fill": (_I, [_P, _I, _L, _P, _P, _I, _P, _P, _I, _L, _P]),
+    "mh_cc_filter": (_I, [_P, _P, _I, _L, C.POINTER(C.c_double), _I, _P]),
 }
 
 

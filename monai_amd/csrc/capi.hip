@@ -25,6 +25,7 @@
 #include "kernels/post.h"
 #include "kernels/metrics.h"
 #include "kernels/edt.h"
+#include "kernels/ccl.h"
 #include "kernels/preproc.h"
 #include "kernels/nn_simple.h"
 #include "kernels/conv1x1_h2.h"
@@ -1928,6 +1929,141 @@ int mh_surface_records(const uint8_t* edges, const void* field, int use_spacing,
     else hipLaunchKernelGGL(surf_partial_kernel<int>, grid, dim3(256), 0, st, edges, (const int*)field, items, write, (double*)workspace, distances, (long long)ndist);
     if (!write) hipLaunchKernelGGL(surf_final_kernel, dim3((unsigned)nitems), dim3(64), 0, st, (const double*)workspace, (int)grid.x, records);
     return launched("surface_records");
+}
+
+// ------------------------------------------------------------------------------------------ connected components (labels, records, keep / fill / filter)
+static_assert(sizeof(CcItem) == MH_CC_ITEM_WORDS * 8, "item table row");
+
+// rows of a host item table: extents >= 1, at most 2^31 - 2 voxels, inside [0, total) of the label buffers and [0, src_elems) of the tensor; with
+// `rules` a known rule and a label count of 0 .. 32.  The largest row and voxel counts come back for the grids
+static int cc_items_ok(const char* who, const int64_t* items, const void* items_dev, int nitems, int64_t total, int64_t src_elems, int rank, bool rules,
+                       int64_t* max_rows, int64_t* max_vox) {
+    if (!items || !items_dev) return fail(MH_ERR_ARG, "%s: null item table", who);
+    if (nitems < 1 || nitems > 65535) return fail(MH_ERR_ARG, "%s: %d items (1 .. 65535)", who, nitems);
+    if (total < 1) return fail(MH_ERR_ARG, "%s: bad total %lld", who, (long long)total);
+    if (rank < 2 || rank > 3) return fail(MH_ERR_ARG, "%s: rank %d (2 or 3)", who, rank);
+    *max_rows = *max_vox = 0;
+    for (int k = 0; k < nitems; ++k) {
+        const int64_t* r = items + (int64_t)k * MH_CC_ITEM_WORDS;
+        int64_t nvox = 1;
+        for (int a = 2; a <= 4; ++a) {
+            if (r[a] < 1 || r[a] > MH_CC_MAX_VOXELS) return fail(MH_ERR_ARG, "%s: item %d has an extent of %lld", who, k, (long long)r[a]);
+            nvox *= r[a];
+            if (nvox > MH_CC_MAX_VOXELS) return fail(MH_ERR_ARG, "%s: item %d has more than %lld voxels (int32 labels)", who, k, (long long)MH_CC_MAX_VOXELS);
+        }
+        if (rank == 2 && r[2] != 1) return fail(MH_ERR_ARG, "%s: item %d has a leading extent of %lld at rank 2", who, k, (long long)r[2]);
+        if (r[0] < 0 || r[0] > total - nvox) return fail(MH_ERR_ARG, "%s: item %d leaves the buffers (offset %lld, %lld voxels, total %lld)", who, k, (long long)r[0], (long long)nvox, (long long)total);
+        if (src_elems >= 0 && (r[1] < 0 || r[1] > src_elems - nvox))
+            return fail(MH_ERR_ARG, "%s: item %d leaves the tensor (offset %lld, %lld voxels, %lld elements)", who, k, (long long)r[1], (long long)nvox, (long long)src_elems);
+        if (rules) {
+            if (r[5] < 0 || r[5] >= CC_NUM_RULES) return fail(MH_ERR_ARG, "%s: item %d has the unknown rule %lld", who, k, (long long)r[5]);
+            if (r[6] < 0 || r[6] > CC_MAX_LABELS) return fail(MH_ERR_ARG, "%s: item %d lists %lld labels (at most %d)", who, k, (long long)r[6], (int)CC_MAX_LABELS);
+        }
+        const int64_t rows = r[2] * r[3];
+        if (rows > *max_rows) *max_rows = rows;
+        if (nvox > *max_vox) *max_vox = nvox;
+    }
+    return MH_OK;
+}
+static int cc_dtype_ok(const char* who, int dtype) {
+    if (dtype != CC_F32 && dtype != CC_U8 && dtype != CC_I64 && dtype != CC_BOOL) return fail(MH_ERR_ARG, "%s: unknown dtype %d", who, dtype);
+    return MH_OK;
+}
+#define MH_CC_DTYPE(dtype, CALL)                  \
+    switch (dtype) {                              \
+    case CC_F32: { CALL(float); } break;          \
+    case CC_I64: { CALL(long long); } break;      \
+    default: { CALL(unsigned char); } break;      \
+    }
+
+int mh_cc_label(const void* src, int dtype, int64_t src_elems, int rank, int connectivity, const int64_t* items_host, const void* items_dev, int nitems,
+                int64_t total, int32_t* labels, void* stream) {
+    if (!src || !labels) return fail(MH_ERR_ARG, "cc_label: null pointer");
+    if (cc_dtype_ok("cc_label", dtype) != MH_OK) return MH_ERR_ARG;
+    if (src_elems < 1) return fail(MH_ERR_ARG, "cc_label: bad element count %lld", (long long)src_elems);
+    int64_t mr, mv;
+    if (cc_items_ok("cc_label", items_host, items_dev, nitems, total, src_elems, rank, true, &mr, &mv) != MH_OK) return MH_ERR_ARG;
+    if (connectivity < 1 || connectivity > rank) return fail(MH_ERR_ARG, "cc_label: connectivity %d at rank %d (1 .. %d)", connectivity, rank, rank);
+    bool multi = false;
+    for (int k = 0; k < nitems; ++k) {      // any item with several classes: the uniting kernel that also compares raw values (it decides per item)
+        const int64_t rule = items_host[(int64_t)k * MH_CC_ITEM_WORDS + 5];
+        multi = multi || rule == CC_LIST_VALUE || rule == CC_VALUE;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const CcItem* items = (const CcItem*)items_dev;
+    const int64_t rblocks = (mr + 3) / 4;
+    const dim3 rgrid((unsigned)(rblocks > 65536 ? 65536 : rblocks), (unsigned)nitems), vgrid(surf_blocks(mv, 8192), (unsigned)nitems);
+#define MH_CC_LABEL(T_)                                                                                                              \
+    hipLaunchKernelGGL((cc_rows_kernel<T_>), rgrid, dim3(256), 0, st, (const T_*)src, items, (int*)labels);                          \
+    if (multi) hipLaunchKernelGGL((cc_unite_kernel<T_, true>), vgrid, dim3(256), 0, st, (const T_*)src, items, connectivity, (int*)labels);   \
+    else hipLaunchKernelGGL((cc_unite_kernel<T_, false>), vgrid, dim3(256), 0, st, (const T_*)src, items, connectivity, (int*)labels)
+    MH_CC_DTYPE(dtype, MH_CC_LABEL)
+#undef MH_CC_LABEL
+    hipLaunchKernelGGL(cc_flatten_kernel, vgrid, dim3(256), 0, st, items, (int*)labels);
+    return launched("cc_label");
+}
+
+int mh_cc_records(const int32_t* labels, int rank, const int64_t* items_host, const void* items_dev, int nitems, int64_t total, int32_t* sizes, uint8_t* border,
+                  void* stream) {
+    if (!labels || !sizes || !border) return fail(MH_ERR_ARG, "cc_records: null pointer");
+    int64_t mr, mv;
+    if (cc_items_ok("cc_records", items_host, items_dev, nitems, total, -1, rank, false, &mr, &mv) != MH_OK) return MH_ERR_ARG;
+    const hipStream_t st = (hipStream_t)stream;
+    const CcItem* items = (const CcItem*)items_dev;
+    const dim3 grid(surf_blocks(mv, 8192), (unsigned)nitems);
+    hipLaunchKernelGGL(cc_zero_kernel, grid, dim3(256), 0, st, items, (int*)sizes, border);
+    const dim3 cgrid(surf_blocks((mv + CC_COUNT_TRIPS - 1) / CC_COUNT_TRIPS, 16384), (unsigned)nitems);       // one wave per chunk of CC_COUNT_TRIPS x 64 voxels
+    hipLaunchKernelGGL(cc_count_kernel, cgrid, dim3(256), 0, st, (const int*)labels, items, rank, (int*)sizes, border);
+    return launched("cc_records");
+}
+
+int mh_cc_keep(void* data, int dtype, int64_t data_elems, const int32_t* labels, const int32_t* keep, int nkeep, int rank, const int64_t* items_host,
+               const void* items_dev, int nitems, int64_t total, void* stream) {
+    if (!data || !labels || !keep) return fail(MH_ERR_ARG, "cc_keep: null pointer");
+    if (cc_dtype_ok("cc_keep", dtype) != MH_OK) return MH_ERR_ARG;
+    if (nkeep < 1 || nkeep > MH_CC_MAX_KEEP) return fail(MH_ERR_ARG, "cc_keep: %d roots per item (1 .. %d)", nkeep, (int)MH_CC_MAX_KEEP);
+    if (data_elems < 1) return fail(MH_ERR_ARG, "cc_keep: bad element count %lld", (long long)data_elems);
+    int64_t mr, mv;
+    if (cc_items_ok("cc_keep", items_host, items_dev, nitems, total, data_elems, rank, false, &mr, &mv) != MH_OK) return MH_ERR_ARG;
+    const dim3 grid(surf_blocks(mv, 8192), (unsigned)nitems);
+#define MH_CC_KEEP(T_) hipLaunchKernelGGL((cc_keep_kernel<T_>), grid, dim3(256), 0, (hipStream_t)stream, (T_*)data, (const int*)labels, (const int*)keep, nkeep, (const CcItem*)items_dev)
+    MH_CC_DTYPE(dtype, MH_CC_KEEP)
+#undef MH_CC_KEEP
+    return launched("cc_keep");
+}
+
+int mh_cc_fill(void* data, int dtype, int64_t data_elems, const int32_t* labels, const uint8_t* border, int rank, const int64_t* items_host, const void* items_dev,
+               int nitems, int64_t total, void* stream) {
+    if (!data || !labels || !border) return fail(MH_ERR_ARG, "cc_fill: null pointer");
+    if (cc_dtype_ok("cc_fill", dtype) != MH_OK) return MH_ERR_ARG;
+    if (data_elems < 1) return fail(MH_ERR_ARG, "cc_fill: bad element count %lld", (long long)data_elems);
+    int64_t mr, mv;
+    if (cc_items_ok("cc_fill", items_host, items_dev, nitems, total, data_elems, rank, false, &mr, &mv) != MH_OK) return MH_ERR_ARG;
+    for (int k = 0; k < nitems; ++k) {
+        const int64_t mode = items_host[(int64_t)k * MH_CC_ITEM_WORDS + 9];
+        if (mode != CC_FILL_VALUE && mode != CC_FILL_BINARY) return fail(MH_ERR_ARG, "cc_fill: item %d has the unknown fill mode %lld", k, (long long)mode);
+    }
+    const dim3 grid(surf_blocks(mv, 8192), (unsigned)nitems);
+#define MH_CC_FILL(T_) hipLaunchKernelGGL((cc_fill_kernel<T_>), grid, dim3(256), 0, (hipStream_t)stream, (T_*)data, (const int*)labels, border, (const CcItem*)items_dev)
+    MH_CC_DTYPE(dtype, MH_CC_FILL)
+#undef MH_CC_FILL
+    return launched("cc_fill");
+}
+
+int mh_cc_filter(const void* src, void* dst, int dtype, int64_t n, const double* labels, int nlabels, void* stream) {
+    if (!src || !dst || (!labels && nlabels > 0)) return fail(MH_ERR_ARG, "cc_filter: null pointer");
+    if (cc_dtype_ok("cc_filter", dtype) != MH_OK) return MH_ERR_ARG;
+    if (n < 1) return fail(MH_ERR_ARG, "cc_filter: bad element count %lld", (long long)n);
+    if (nlabels < 0 || nlabels > CC_MAX_LABELS) return fail(MH_ERR_ARG, "cc_filter: %d labels (0 .. %d)", nlabels, (int)CC_MAX_LABELS);
+    CcLabels ls;
+    memset(&ls, 0, sizeof(ls));
+    ls.n = nlabels;
+    for (int k = 0; k < nlabels; ++k) ls.lab[k] = labels[k];
+    const dim3 grid(surf_blocks(n, 8192));
+#define MH_CC_FILTER(T_) hipLaunchKernelGGL((cc_filter_kernel<T_>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)src, (T_*)dst, (long long)n, ls)
+    MH_CC_DTYPE(dtype, MH_CC_FILTER)
+#undef MH_CC_FILTER
+    return launched("cc_filter");
 }
 
 // ------------------------------------------------------------------------------------------ Gaussian smoothing

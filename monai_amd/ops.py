@@ -1283,3 +1283,104 @@ def surface_records(pred: torch.Tensor, truth: torch.Tensor, num_classes: int, s
         for i, key in enumerate(r_keys):
             distances[key] = dist_h[int(offs[i]):int(offs[i + 1])]
     return SurfaceRecords(present, records, distances, reads)
+
+
+# ------------------------------------------------------------------------------------------ connected components: labels, records, keep / fill / filter
+CC_GT, CC_EQ, CC_NE, CC_LIST_VALUE, CC_LIST_ANY, CC_VALUE = range(6)
+CC_FILL_VALUE, CC_FILL_BINARY = 0, 1
+CC_MAX_LABELS = 32
+_CC_WORDS = 48
+
+
+class CcItems:
+    """The item table of the connected-component kernels (include/monai_amd.h, MH_CC_ITEM_WORDS): one row per volume of `spatial` (two or three axes).
+    A row is a dict: ``src`` element offset of the volume in the tensor; ``off`` voxel offset in the label / record buffers (default: row k at k * n);
+    ``rule`` CC_GT / CC_EQ / CC_NE with ``v``, CC_LIST_VALUE / CC_LIST_ANY with ``labels`` (at most 32, distinct), CC_VALUE (every non-zero value its
+    own class); rows of one table may use different rules; ``fill`` and ``fill_mode`` for `cc_fill`."""
+
+    def __init__(self, spatial: Sequence[int], rows: Sequence[dict], device):
+        import numpy as np
+
+        sp = [int(v) for v in spatial]
+        if len(sp) not in (2, 3) or min(sp) < 1:
+            raise NotImplementedError(f"monai_amd.cc: two or three non-empty spatial axes are what the HIP path takes, got {tuple(sp)}")
+        if not rows:
+            raise RuntimeError("monai_amd.cc: an empty item table")
+        self.rank, self.vol = len(sp), [1] * (3 - len(sp)) + sp
+        self.spatial, self.n = tuple(sp), sp[0] * sp[1] * (sp[2] if len(sp) == 3 else 1)
+        host = np.zeros((len(rows), _CC_WORDS), dtype=np.int64)
+        fl = host.view(np.float64)
+        for k, r in enumerate(rows):
+            labels = [float(v) for v in r.get("labels", ())]
+            if len(labels) > CC_MAX_LABELS or len(set(labels)) != len(labels):
+                raise RuntimeError(f"monai_amd.cc: at most {CC_MAX_LABELS} distinct labels per item, got {labels}")
+            host[k, 0:7] = (r.get("off", k * self.n), r["src"], self.vol[0], self.vol[1], self.vol[2], r.get("rule", CC_GT), len(labels))
+            fl[k, 7], fl[k, 8] = float(r.get("v", 0.0)), float(r.get("fill", 0.0))
+            host[k, 9] = r.get("fill_mode", CC_FILL_VALUE)
+            fl[k, 16:16 + len(labels)] = labels
+        self.host, self.dev = host, torch.from_numpy(host).to(device)
+        self.nitems, self.total = len(rows), int(host[:, 0].max()) + self.n
+
+    def args(self):
+        return self.host.ctypes.data_as(C.c_void_p), _lib.ptr(self.dev), self.nitems, self.total
+
+
+def _cc_tensor(t: torch.Tensor, who: str) -> int:
+    _lib.require_device(t, dtypes=tuple(_ED_DTYPES))
+    if not t.is_contiguous():
+        raise RuntimeError(f"monai_amd.{who}: a contiguous tensor is required")
+    return _ED_DTYPES[t.dtype]
+
+
+def cc_label(src: torch.Tensor, items: CcItems, connectivity: int) -> torch.Tensor:
+    """DEVICE int32 [items.total]: for every item the connected components of its volume of `src` (float32 / uint8 / int64 / bool) under the item's
+    rule -- 0 for background, otherwise 1 + the linear index inside the item of the component's first voxel in C order, the same bits on every run.
+    Neighbours lie within `connectivity` orthogonal hops (1 .. rank), as skimage.measure.label / scipy's generate_binary_structure define it
+    (csrc/kernels/ccl.h; monai/transforms/utils.py:1134-1180).  CC_LIST_VALUE labels every listed class of a label map in the one pass.  No host read."""
+    dt = _cc_tensor(src, "cc_label")
+    labels = torch.empty(items.total, dtype=torch.int32, device=src.device)
+    _lib.lib().call("mh_cc_label", _lib.ptr(src), dt, src.numel(), items.rank, int(connectivity), *items.args(), _lib.ptr(labels), _s(src))
+    return labels
+
+
+def cc_records(labels: torch.Tensor, items: CcItems):
+    """(sizes int32 [total], border bool [total]) at ROOT positions (index label - 1 inside the item), zero elsewhere: the component's voxel count
+    and whether it touches the border of the volume along the item's own axes.  No host read."""
+    _lib.require_device(labels, dtypes=(torch.int32,))
+    sizes = torch.empty(items.total, dtype=torch.int32, device=labels.device)
+    border = torch.empty(items.total, dtype=torch.uint8, device=labels.device)
+    _lib.lib().call("mh_cc_records", _lib.ptr(labels), items.rank, *items.args(), _lib.ptr(sizes), _lib.ptr(border), _s(labels))
+    return sizes, border.view(torch.bool)
+
+
+def cc_keep(data: torch.Tensor, labels: torch.Tensor, keep: torch.Tensor, items: CcItems) -> torch.Tensor:
+    """In place: every voxel of an item with a label > 0 that is not in keep[item] (DEVICE int32 [nitems, k], entries <= 0 are padding) becomes 0 in
+    `data` at the item's ``src`` offset.  No host read."""
+    dt = _cc_tensor(data, "cc_keep")
+    _lib.require_device(labels, keep, dtypes=(torch.int32,))
+    if keep.dim() != 2 or keep.shape[0] != items.nitems or not keep.is_contiguous():
+        raise RuntimeError(f"monai_amd.cc_keep: keep must be a contiguous int32 [{items.nitems}, k] tensor, got {tuple(keep.shape)}")
+    _lib.lib().call("mh_cc_keep", _lib.ptr(data), dt, data.numel(), _lib.ptr(labels), _lib.ptr(keep), int(keep.shape[1]), items.rank, *items.args(), _s(data))
+    return data
+
+
+def cc_fill(data: torch.Tensor, labels: torch.Tensor, border: torch.Tensor, items: CcItems) -> torch.Tensor:
+    """In place: per item, CC_FILL_VALUE writes the item's ``fill`` into every voxel of a component that does not touch the border; CC_FILL_BINARY
+    rewrites the volume as 1 where the label is 0 or the component is enclosed, 0 elsewhere (monai/transforms/utils.py:1544-1558).  No host read."""
+    dt = _cc_tensor(data, "cc_fill")
+    _lib.require_device(labels, dtypes=(torch.int32,))
+    _lib.require_device(border, dtypes=(torch.bool, torch.uint8))
+    _lib.lib().call("mh_cc_fill", _lib.ptr(data), dt, data.numel(), _lib.ptr(labels), _lib.ptr(border), items.rank, *items.args(), _s(data))
+    return data
+
+
+def cc_filter(src: torch.Tensor, labels: Sequence[float]) -> torch.Tensor:
+    """A new tensor: the values of `src` that are in `labels` (at most 32), 0 elsewhere (LabelFilter, monai/transforms/post/array.py:474-500)."""
+    dt = _cc_tensor(src, "cc_filter")
+    vals = [float(v) for v in labels]
+    if len(vals) > CC_MAX_LABELS:
+        raise NotImplementedError(f"monai_amd.cc_filter: at most {CC_MAX_LABELS} labels on the HIP path, got {len(vals)}")
+    out = torch.empty_like(src)
+    if src.numel():
+        _lib.lib().call("mh_cc_filter", _lib.ptr(src), _lib.ptr(out), dt, src.numel(), (C.c_double * max(len(vals), 1))(*vals), len(vals), _s(src))
+    return out

@@ -82,6 +82,7 @@ _TARGETS = {
         "Activations": ("monai_amd.transforms.post.array", "Activations"),
         "AsDiscrete": ("monai_amd.transforms.post.array", "AsDiscrete"),
         "DistanceTransformEDT": ("monai_amd.transforms.post.array", "DistanceTransformEDT"),
+        **{n: ("monai_amd.transforms.post.array", n) for n in ("KeepLargestConnectedComponent", "FillHoles", "LabelFilter")},
     },
     "monai.transforms.post.dictionary": {
         "Activationsd": ("monai_amd.transforms.post.dictionary", "Activationsd"),
@@ -93,6 +94,8 @@ _TARGETS = {
         "DistanceTransformEDTd": ("monai_amd.transforms.post.dictionary", "DistanceTransformEDTd"),
         "DistanceTransformEDTD": ("monai_amd.transforms.post.dictionary", "DistanceTransformEDTd"),
         "DistanceTransformEDTDict": ("monai_amd.transforms.post.dictionary", "DistanceTransformEDTd"),
+        **{n + suffix: ("monai_amd.transforms.post.dictionary", n + "d") for n in ("KeepLargestConnectedComponent", "FillHoles", "LabelFilter")
+           for suffix in ("d", "D", "Dict")},
     },
     "monai.transforms.intensity.dictionary": {
         "GaussianSmoothd": ("monai_amd.transforms.intensity.dictionary", "GaussianSmoothd"),
@@ -127,7 +130,8 @@ _TARGETS = {
     "monai.metrics.hausdorff_distance": {n: ("monai_amd.metrics.hausdorff_distance", n) for n in ("HausdorffDistanceMetric", "compute_hausdorff_distance")},
     "monai.metrics.surface_distance": {n: ("monai_amd.metrics.surface_distance", n) for n in ("SurfaceDistanceMetric", "compute_average_surface_distance")},
     "monai.metrics.surface_dice": {n: ("monai_amd.metrics.surface_dice", n) for n in ("SurfaceDiceMetric", "compute_surface_dice")},
-    "monai.transforms.utils": {"distance_transform_edt": ("monai_amd.transforms.utils", "distance_transform_edt")},
+    "monai.transforms.utils": {n: ("monai_amd.transforms.utils", n) for n in
+                               ("distance_transform_edt", "get_largest_connected_component_mask", "fill_holes", "get_unique_labels")},
 }
 # parent packages that re-export the names above
 _REEXPORT = ["monai.inferers", "monai.networks.nets", "monai.transforms", "monai.networks.layers", "monai.networks.blocks", "monai.metrics"]

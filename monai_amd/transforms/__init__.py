@@ -12,5 +12,7 @@ from .spatial import Flip, FlipD, FlipDict, Flipd, Rotate90, Rotate90D, Rotate90
 from .spatial import Orientation, OrientationD, OrientationDict, Orientationd, Resample, SpatialResample, Spacing, SpacingD, SpacingDict, Spacingd, spatial_resample  # noqa: F401
 from .post import Activations, ActivationsD, ActivationsDict, Activationsd, AsDiscrete, AsDiscreteD, AsDiscreteDict, AsDiscreted  # noqa: F401
 from .post import DistanceTransformEDT, DistanceTransformEDTD, DistanceTransformEDTDict, DistanceTransformEDTd  # noqa: F401
-from .utils import distance_transform_edt  # noqa: F401
+from .post import FillHoles, FillHolesD, FillHolesDict, FillHolesd, LabelFilter, LabelFilterD, LabelFilterDict, LabelFilterd  # noqa: F401
+from .post import KeepLargestConnectedComponent, KeepLargestConnectedComponentD, KeepLargestConnectedComponentDict, KeepLargestConnectedComponentd  # noqa: F401
+from .utils import distance_transform_edt, fill_holes, get_largest_connected_component_mask, get_unique_labels  # noqa: F401
 from .lazy import ApplyPending, ApplyPendingd, apply_pending, apply_pending_transforms  # noqa: F401

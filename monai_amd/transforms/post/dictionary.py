@@ -9,10 +9,11 @@ from __future__ import annotations
 from collections.abc import Callable, Hashable, Mapping, Sequence
 
 from ...utils.misc import ensure_tuple, ensure_tuple_rep
-from .array import Activations, AsDiscrete, DistanceTransformEDT
+from .array import Activations, AsDiscrete, DistanceTransformEDT, FillHoles, KeepLargestConnectedComponent, LabelFilter
 
 __all__ = ["Activationsd", "ActivationsD", "ActivationsDict", "AsDiscreted", "AsDiscreteD", "AsDiscreteDict", "DistanceTransformEDTd", "DistanceTransformEDTD",
-           "DistanceTransformEDTDict"]
+           "DistanceTransformEDTDict", "KeepLargestConnectedComponentd", "KeepLargestConnectedComponentD", "KeepLargestConnectedComponentDict", "FillHolesd",
+           "FillHolesD", "FillHolesDict", "LabelFilterd", "LabelFilterD", "LabelFilterDict"]
 
 
 class _PerKey:
@@ -81,6 +82,43 @@ class DistanceTransformEDTd(_PerKey):
         self.distance_transform = self.converter = DistanceTransformEDT(sampling=sampling)
 
 
+class KeepLargestConnectedComponentd(_PerKey):
+    """monai/transforms/post/dictionary.py:213-268"""
+
+    array_transform = KeepLargestConnectedComponent
+
+    def __init__(self, keys, applied_labels=None, is_onehot: bool | None = None, independent: bool = True, connectivity: int | None = None,
+                 num_components: int = 1, allow_missing_keys: bool = False) -> None:
+        self._bind(keys, allow_missing_keys, {})
+        self.converter = KeepLargestConnectedComponent(applied_labels=applied_labels, is_onehot=is_onehot, independent=independent, connectivity=connectivity,
+                                                       num_components=num_components)
+
+
+class LabelFilterd(_PerKey):
+    """monai/transforms/post/dictionary.py:312-337"""
+
+    _mh_numpy_to_reference = True
+
+    def __init__(self, keys, applied_labels, allow_missing_keys: bool = False) -> None:
+        self.keys, self.allow_missing_keys, self._columns = ensure_tuple(keys), allow_missing_keys, ()      # LabelFilter has no default constructor for _bind
+        if not self.keys:
+            raise ValueError("keys must be non empty.")
+        self.converter = LabelFilter(applied_labels)
+
+
+class FillHolesd(_PerKey):
+    """monai/transforms/post/dictionary.py:340-375"""
+
+    array_transform = FillHoles
+
+    def __init__(self, keys, applied_labels=None, connectivity: int | None = None, allow_missing_keys: bool = False) -> None:
+        self._bind(keys, allow_missing_keys, {})
+        self.converter = FillHoles(applied_labels=applied_labels, connectivity=connectivity)
+
+
 ActivationsD = ActivationsDict = Activationsd
+KeepLargestConnectedComponentD = KeepLargestConnectedComponentDict = KeepLargestConnectedComponentd
+FillHolesD = FillHolesDict = FillHolesd
+LabelFilterD = LabelFilterDict = LabelFilterd
 DistanceTransformEDTD = DistanceTransformEDTDict = DistanceTransformEDTd
 AsDiscreteD = AsDiscreteDict = AsDiscreted
