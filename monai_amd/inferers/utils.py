@@ -18,11 +18,13 @@ windows and one RCCL all-gather of the logits precedes the (replicated, determin
 
 from __future__ import annotations
 
+import itertools
+import math
 import os
 import threading
 import warnings
 from collections.abc import Callable, Mapping, Sequence
-from typing import Any
+from typing import Any, NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -115,6 +117,52 @@ def _auto_batch(predictor, roi3, num_win: int, sw_batch_size: int, device, world
     return cap
 
 
+class _Geometry(NamedTuple):
+    """The window geometry of one (sub-)volume, computed once per volume: the whole volume, or each slab's sub-volume (`_slabwise`)."""
+
+    spatial: tuple       # the volume's own spatial size
+    roi_size: tuple
+    image_size: tuple    # after the padding up to the roi
+    pad_size: tuple      # in F.pad's order (last dim first); all zero when the volume is at least the roi
+    starts: list         # per axis, the window starts
+    num_win: int
+    roi3: tuple          # roi_size / image_size / starts as the kernels' 3-D view
+    img3: tuple
+    grid3: list
+
+
+def _geometry(spatial, roi_size, overlap) -> _Geometry:
+    nsd = len(spatial)
+    # pad when the image is smaller than the roi (utils.py:163-170), centred, last dim first
+    image_size = tuple(max(spatial[i], roi_size[i]) for i in range(nsd))
+    pad_size = []
+    for k in range(nsd - 1, -1, -1):
+        diff = max(roi_size[k] - spatial[k], 0)
+        pad_size.extend([diff // 2, diff - diff // 2])
+    starts = window_starts(image_size, roi_size, _get_scan_interval(image_size, roi_size, nsd, overlap))
+    return _Geometry(tuple(spatial), tuple(roi_size), image_size, tuple(pad_size), starts, math.prod(len(s) for s in starts), _to3(roi_size, 1),
+                     _to3(image_size, 1), [[0]] * (3 - nsd) + [list(s) for s in starts])
+
+
+class _Call(NamedTuple):
+    """What one public call asks of every (sub-)volume it runs: its arguments after the checks, with the private keyword taken out of `kwargs`."""
+
+    predictor: Callable[..., Any]
+    args: tuple
+    kwargs: dict
+    process_fn: Callable | None
+    with_coord: bool
+    sw_batch_size: int
+    progress: bool
+    argmax_dtype: Any    # fused AsDiscrete(argmax=True) epilogue (sliding_window_argmax below): the labels' dtype, else None
+    fused: bool          # the predictor writes its logits itself (`forward_into` / `forward_into_windows`) and takes nothing but the windows
+    imp: torch.Tensor    # importance map of the roi on the host, and the cache key of a map this module evaluated itself (a caller's roi_weight_map is uploaded per call)
+    imp_key: tuple | None
+    mode: str
+    sigma_scale: Any
+    out_device: torch.device
+
+
 @function_fallback("monai.inferers.utils", "sliding_window_inference")
 def sliding_window_inference(
     inputs: torch.Tensor,
@@ -153,32 +201,23 @@ def sliding_window_inference(
     instead of ``sw_batch_size`` -- result-neutral, but it changes peak memory; MONAI_AMD_STRICT_SW_BATCH=1 keeps the caller's value
     and MONAI_AMD_SW_BATCH=n sets it.  ``process_fn`` (utils.py:232-234) is honoured with
     the reference's semantics: each batch is multiplied by the weight map it returns, the count map uses the first batch's.
+
+    One call makes one pass: check and normalise the arguments, plan the windows (``_geometry``), run (``_run_volume``; when the logits do not fit: the buffered
+    order falls back to the plain one, the whole volume to ``_slabwise``), give the result the caller's dtype and tensor type.
     """
     num_spatial_dims = inputs.dim() - 2
-    buffered = buffer_steps is not None and buffer_steps > 0
-    if buffered:
+    argmax_dtype = kwargs.pop("_monai_amd_argmax", None)      # the one private keyword (sliding_window_argmax, inferers/inferer.py); what is left is the predictor's own
+    buffer = None                                             # (axis, steps) of the reference's buffered schedule
+    if buffer_steps is not None and buffer_steps > 0:
         if buffer_dim < -num_spatial_dims or buffer_dim > num_spatial_dims:
             raise ValueError(f"buffer_dim must be in [{-num_spatial_dims}, {num_spatial_dims}], got {buffer_dim}.")
         if buffer_dim < 0:
             buffer_dim += num_spatial_dims
         if buffer_dim >= num_spatial_dims:
             raise NotImplementedError("monai_amd: buffer_steps with buffer_dim == the number of spatial dims is not on the HIP path")
-        if kwargs.get("_monai_amd_argmax") is not None:       # rejected BEFORE any window is predicted (a fall-through would otherwise predict them all twice)
+        if argmax_dtype is not None:       # rejected BEFORE any window is predicted (a fall-through would otherwise predict them all twice)
             raise NotImplementedError("monai_amd: the fused argmax epilogue with buffer_steps is not on the HIP path (blend in the buffered order, then AsDiscrete)")
-        if not kwargs.pop("_monai_amd_buffered_inner", False):
-            # `buffer_steps` is the reference's MEMORY-SAVING option: the callers who pass it are the ones with large volumes.  The buffered summation order
-            # needs the logits of all windows resident; when they do not fit, the volume goes through the plain order slab by slab (bit-identical to the
-            # reference's plain run, which differs from its buffered run by roundings <= 1e-6 -- tests/golden/buffered.npz) instead of failing.
-            common = (roi_size, sw_batch_size, predictor, overlap, mode, sigma_scale, padding_mode, cval, sw_device, device, progress, roi_weight_map, process_fn)
-            try:
-                return sliding_window_inference(inputs, *common, buffer_steps, buffer_dim, with_coord, *args, _monai_amd_buffered_inner=True, **kwargs)
-            except _LogitsDoNotFit as e:
-                if process_fn is not None or with_coord:      # no slab-wise form exists for these (their semantics are tied to the whole volume): the plain retry could only
-                    raise                                     # repeat the predictor calls already made and fail the same way
-                reason = str(e).split(" (")[0]
-            warnings.warn(f"{reason}: buffer_steps={buffer_steps} is served in the plain summation order, slab by slab "
-                          "(equal to the reference's unbuffered result; its buffered result differs from that by roundings)")
-            return sliding_window_inference(inputs, *common, None, -1, with_coord, *args, **kwargs)
+        buffer = (buffer_dim, int(buffer_steps))
     overlap = ensure_tuple_rep(overlap, num_spatial_dims)
     for o in overlap:
         if o < 0 or o >= 1:
@@ -188,127 +227,194 @@ def sliding_window_inference(
     meta_src = inputs if (type(inputs) is not torch.Tensor and hasattr(inputs, "as_tensor")) else None
     if meta_src is not None:
         inputs = inputs.as_tensor()
-    # drop-in input handling (utils.py:146-153 take any float dtype and any inputs/sw_device pair): half / bfloat16 volumes are
-    # widened to fp32 for the kernels and the result is returned in the caller's dtype; a CPU volume with a ROCm `sw_device` is
-    # moved to HBM once (the reference moves it window by window) and the result goes back to `device` or the inputs' device
     if torch.is_grad_enabled() and inputs.requires_grad:
         # the reference's result carries the autograd graph of the windows (tests/inferers/test_sliding_window_inference.py:124-139);
         # the kernels do not record one: such a call belongs to the reference path
         raise NotImplementedError("monai_amd: sliding_window_inference of an input that requires grad (autograd through the blend) is not on the HIP path")
+    # drop-in input handling (utils.py:146-153 take any float dtype and any inputs/sw_device pair): half / bfloat16 volumes are
+    # widened to fp32 for the kernels and the result is returned in the caller's dtype; a CPU volume with a ROCm `sw_device` is
+    # moved to HBM once (the reference moves it window by window) and the result goes back to `device` or the inputs' device
+    out_device = torch.device(device) if device is not None else inputs.device
     narrow = inputs.dtype if inputs.dtype in (torch.float16, torch.bfloat16) else None
     host_in = (not inputs.is_cuda) and sw_device is not None and torch.device(sw_device).type == "cuda"
     if narrow is not None or host_in:
-        x = inputs.to(device=torch.device(sw_device) if host_in else inputs.device, dtype=torch.float32)
-        out = sliding_window_inference(x, roi_size, sw_batch_size, predictor, overlap, mode, sigma_scale, padding_mode, cval, sw_device,
-                                       device if device is not None else inputs.device, progress, roi_weight_map, process_fn, buffer_steps,
-                                       buffer_dim, with_coord, *args, **kwargs)
+        inputs = inputs.to(device=torch.device(sw_device) if host_in else inputs.device, dtype=torch.float32)
+    _lib.require_device(inputs)
+    if sw_device is not None and torch.device(sw_device).type != inputs.device.type:
+        raise RuntimeError("monai_amd: sw_device must be the ROCm device of the inputs (windows are gathered in HBM)")
+
+    roi_size = fall_back_tuple(roi_size, inputs.shape[2:])
+    geo = _geometry(tuple(inputs.shape[2:]), roi_size, overlap)
+    if any(geo.pad_size):
+        inputs = F.pad(inputs, pad=list(geo.pad_size), mode=look_up_option(padding_mode, _PAD_MODES, "padding_mode"), value=cval)
+    inputs = inputs.contiguous()
+
+    # importance map, always evaluated on the host in fp32 (bit-identical to the reference's CPU map)
+    valid_patch_size = get_valid_patch_size(geo.image_size, roi_size)
+    imp, imp_key = roi_weight_map, None
+    if valid_patch_size != tuple(roi_size) or roi_weight_map is None:
+        try:
+            imp, imp_key = _host_importance_map(valid_patch_size, mode, sigma_scale, inputs.dtype)
+        except Exception as e:  # same wrapping as the reference (utils.py:205-209)
+            raise RuntimeError(
+                f"patch size {valid_patch_size}, mode={mode}, sigma_scale={sigma_scale}, device={device}\n"
+                "Seems to be OOM. Please try smaller patch size or mode='constant' instead of mode='gaussian'."
+            ) from e
+    imp = imp.to(dtype=inputs.dtype)
+    while imp.dim() > num_spatial_dims:
+        imp = imp[0]
+
+    fused = (hasattr(predictor, "forward_into") and hasattr(predictor, "out_channels") and getattr(predictor, "window_sized_output", True)
+             and not with_coord and not args and not kwargs and process_fn is None)
+    call = _Call(predictor, args, kwargs, process_fn, with_coord, sw_batch_size, progress, argmax_dtype, fused, imp, imp_key, mode, sigma_scale, out_device)
+
+    def finish(out):      # the caller's dtype and tensor type
         keys, parts = _flatten_struct(out)
         if narrow is not None:
             parts = [t.to(narrow) if t.is_floating_point() else t for t in parts]
         if meta_src is not None:
             parts = [_restore_meta(t, meta_src) for t in parts]
         return _pack_struct(parts, keys)
-    _lib.require_device(inputs)
-    compute_dtype = inputs.dtype
-    batch_size, in_ch, *image_size_ = inputs.shape
-    out_device = torch.device(device) if device is not None else inputs.device
-    if sw_device is not None and torch.device(sw_device).type != inputs.device.type:
-        raise RuntimeError("monai_amd: sw_device must be the ROCm device of the inputs (windows are gathered in HBM)")
-    roi_size = fall_back_tuple(roi_size, image_size_)
 
-    # pad when the image is smaller than the roi (utils.py:163-170), centred, last dim first
-    image_size = tuple(max(image_size_[i], roi_size[i]) for i in range(num_spatial_dims))
-    pad_size = []
-    for k in range(inputs.dim() - 1, 1, -1):
-        diff = max(roi_size[k - 2] - inputs.shape[k], 0)
-        half = diff // 2
-        pad_size.extend([half, diff - half])
-    if any(pad_size):
-        inputs = F.pad(inputs, pad=pad_size, mode=look_up_option(padding_mode, _PAD_MODES, "padding_mode"), value=cval)
-    inputs = inputs.contiguous()
-
-    scan_interval = _get_scan_interval(image_size, roi_size, num_spatial_dims, overlap)
-    starts = window_starts(image_size, roi_size, scan_interval)
-    num_win = 1
-    for s in starts:
-        num_win *= len(s)
-
-    # all-window logits that do not fit in HBM: slab by slab along the first spatial axis (see _slabwise)
-    argmax_dtype = kwargs.pop("_monai_amd_argmax", None)      # fused AsDiscrete(argmax=True) epilogue (sliding_window_argmax below)
-    slab_ok = (not kwargs.pop("_monai_amd_no_slabs", False) and not with_coord and process_fn is None and not any(pad_size)
-               and len(starts[0]) > 1 and not buffered)
-    if slab_ok:
-        sub_kwargs = dict(kwargs, _monai_amd_no_slabs=True, _monai_amd_argmax=argmax_dtype)
-
-        def _whole(x):
-            return sliding_window_inference(x, roi_size, sw_batch_size, predictor, overlap, mode, sigma_scale, padding_mode, cval, sw_device,
-                                            device, progress, roi_weight_map, None, buffer_steps, buffer_dim, False, *args, **sub_kwargs)
-
+    if buffer is not None:
+        # `buffer_steps` is the reference's MEMORY-SAVING option: the callers who pass it are the ones with large volumes.  The buffered summation order
+        # needs the logits of all windows resident; when they do not fit, the volume goes through the plain order slab by slab (bit-identical to the
+        # reference's plain run, which differs from its buffered run by roundings <= 1e-6 -- tests/golden/buffered.npz) instead of failing.
         try:
-            return _whole(meta_src if meta_src is not None else inputs)
-        except _LogitsDoNotFit as e:      # leave the handler before retrying: the traceback keeps the failed call's buffers alive
-            need, budget = e.need, (0.9 * e.budget if _logits_budget(inputs.device) is None else e.budget)
-        out = _slabwise(inputs, roi_size, starts[0], need, budget, _whole)
-        if meta_src is not None:
-            keys, parts = _flatten_struct(out)
-            out = _pack_struct([_restore_meta(t, meta_src) for t in parts], keys)
-        return out
+            return finish(_run_volume(inputs, geo, call, buffer))
+        except _LogitsDoNotFit as e:
+            if process_fn is not None or with_coord:      # no slab-wise form exists for these (their semantics are tied to the whole volume)
+                raise
+            reason = str(e).split(" (")[0]
+        warnings.warn(f"{reason}: buffer_steps={buffer_steps} is served in the plain summation order, slab by slab "
+                      "(equal to the reference's unbuffered result; its buffered result differs from that by roundings)")
+    try:
+        return finish(_run_volume(inputs, geo, call, None))
+    except _LogitsDoNotFit as e:      # leave the handler before retrying: the traceback keeps the failed call's buffers alive
+        # all-window logits that do not fit in HBM: slab by slab along the first spatial axis (see _slabwise)
+        if with_coord or process_fn is not None or any(geo.pad_size) or len(geo.starts[0]) < 2:
+            raise
+        need, budget = e.need, (0.9 * e.budget if _logits_budget(inputs.device) is None else e.budget)
 
-    # importance map, always evaluated on the host in fp32 (bit-identical to the reference's CPU map)
-    valid_patch_size = get_valid_patch_size(image_size, roi_size)
-    imp_key = None          # cache key of a map this module evaluated itself (a caller's roi_weight_map is uploaded per call)
-    if valid_patch_size == tuple(roi_size) and roi_weight_map is not None:
-        imp = roi_weight_map
-    else:
-        try:
-            imp, imp_key = _host_importance_map(valid_patch_size, mode, sigma_scale, compute_dtype)
-        except Exception as e:  # same wrapping as the reference (utils.py:205-209)
-            raise RuntimeError(
-                f"patch size {valid_patch_size}, mode={mode}, sigma_scale={sigma_scale}, device={device}\n"
-                "Seems to be OOM. Please try smaller patch size or mode='constant' instead of mode='gaussian'."
-            ) from e
-    imp = imp.to(dtype=compute_dtype)
-    while imp.dim() > num_spatial_dims:
-        imp = imp[0]
+    def sub_volume(x):
+        return _run_volume(x.contiguous(), _geometry(tuple(x.shape[2:]), roi_size, overlap), call, None)
 
-    roi3 = _to3(roi_size, 1)
-    img3 = _to3(image_size, 1)
-    grid3 = [[0]] * (3 - num_spatial_dims) + [list(s) for s in starts]
-    dev = inputs.device
+    return finish(_slabwise(inputs, roi_size, geo.starts[0], need, budget, sub_volume))
+
+
+def _channels(store) -> int:
+    return store.k if isinstance(store, ops.LogitsMosaic) else int(store.shape[1])
+
+
+class _WindowLogits:
+    """The logits of every window of an image and what is known of the predictor's outputs.  `open` allocates them, once: from `out_channels` before the first
+    predictor call where the predictor has it (the fit decision is then taken before a predictor or `process_fn` has seen a batch: neither may see one twice),
+    else from the first prediction.  `predict` fills the rows of one batch of windows."""
+
+    def __init__(self, call: _Call, geo: _Geometry, shard, nb: int, buffer, first_only: bool, dtype, dev):
+        self.call, self.geo, self.shard, self.nb, self.buffer, self.first_only, self.dtype, self.dev = call, geo, shard, nb, buffer, first_only, dtype, dev
+        self.stores = None        # per output: window-major rows [num_win_padded, K, *seg3] (`_alloc_logits`), or the mosaic layout (`_alloc_mosaic`)
+        self.seg_shapes = None    # per output: spatial shape of one window's prediction (native dims)
+        self.zscales = None       # per output: None at the windows' resolution, else prediction size / roi per axis
+        self.dict_keys = None
+        self.proc_weights = None  # process_fn: per output, the weight map behind the count map (the caller takes it from the first batch / the first flush)
+        self.imp_dev = call.imp.to(dev) if call.process_fn is not None else None
+
+    def open(self, channels, seg_shapes) -> None:
+        c, geo = self.call, self.geo
+        self.stores = []
+        for k, sh in zip(channels, seg_shapes):
+            # fused on one GPU in the plain order: the mosaic layout when the path allows it (the network's last kernel writes it directly)
+            mosaic = _alloc_mosaic(c.predictor, self.shard, c.argmax_dtype, k, geo.grid3, geo.roi3, self.dtype, self.dev) if c.fused and self.buffer is None else None
+            self.stores.append(mosaic if mosaic is not None else _alloc_logits(self.shard, self.nb, k, _to3(sh, 1), self.dtype, self.dev))
+        self.seg_shapes = [tuple(sh) for sh in seg_shapes]
+        self.zscales = [None if sh == geo.roi_size else [o / float(i) for o, i in zip(sh, geo.roi_size)] for sh in self.seg_shapes]
+
+    def predict(self, win_data: torch.Tensor, coords, runs) -> list:
+        """Call the predictor on `win_data` (with `coords` under with_coord), then `process_fn`; write the (weighted) predictions to the rows `runs` = [(first row,
+        count)] of every output, consecutive batch elements to consecutive runs.  -> per output the weight map `process_fn` returned, [] without one."""
+        c = self.call
+        seg_out = c.predictor(win_data, *(() if coords is None else (coords,)), *c.args, **c.kwargs)
+        self.dict_keys, segs = _flatten_struct(seg_out)
+        w = None
+        if c.process_fn is not None:     # utils.py:232-238: the callback may edit the predictions and the weight map
+            segs, w = c.process_fn(segs, win_data, self.imp_dev)
+            segs = tuple(segs) if isinstance(segs, (list, tuple)) else (segs,)
+            if w.dim() == len(self.geo.roi_size):
+                w = w[None, None]
+            w = w.to(dtype=self.dtype, device=self.dev)
+        if self.first_only:              # the reference's buffered schedule keeps the first output only (utils.py:244)
+            self.dict_keys, segs = self.dict_keys and self.dict_keys[:1], segs[:1]
+        if self.buffer is not None and (len(segs) != 1 or tuple(segs[0].shape[2:]) != self.geo.roi_size):
+            raise NotImplementedError("monai_amd: buffer_steps with several / multi-resolution predictor outputs is not on the HIP path (the reference fails there too)")
+        if self.stores is None:
+            self.open([int(s.shape[1]) for s in segs], [s.shape[2:] for s in segs])
+        weights = []
+        for s, store, sh, z in zip(segs, self.stores, self.seg_shapes, self.zscales):
+            if int(s.shape[1]) != _channels(store):
+                raise RuntimeError(f"monai_amd: the predictor returned {int(s.shape[1])} channels, the logits were sized for {_channels(store)} (its `out_channels`, or its first batch)")
+            if s.dtype != self.dtype and s.is_floating_point():
+                # a predictor under torch.autocast returns half precision; the reference weights it in that precision and
+                # accumulates in compute_dtype (utils.py:286-288) -- here it is widened first (never less precise)
+                s = s.to(self.dtype)
+            _lib.require_device(s)
+            if w is not None:
+                if z is not None:        # cumulative nearest resampling, as utils.py:260-263
+                    w = F.interpolate(w, sh, mode=_NEAREST)
+                if not self.first_only and (w.shape[0] != 1 or w.shape[1] != 1):
+                    raise RuntimeError("monai_amd: process_fn must return a weight map broadcastable over batch and channels "
+                                       f"(got {tuple(w.shape)}; the reference's count map needs [1, 1, *spatial])")
+                weights.append(w)
+            k = 0
+            for r0, n in runs:
+                dst = store[r0 : r0 + n]
+                src = s[k : k + n].reshape(dst.shape)
+                if w is None:
+                    dst.copy_(src)
+                else:                    # `seg *= w_t`
+                    torch.mul(src, (w if w.shape[0] == 1 else w[k : k + n]).reshape((-1, w.shape[1]) + tuple(dst.shape[2:])), out=dst)
+                k += n
+        return weights
+
+    def count_from(self, weights) -> None:
+        """the reference builds its count map once, from the weight map current then (utils.py:264-275)"""
+        self.proc_weights = [w[0, 0].reshape(_to3(sh, 1)).contiguous().clone() for w, sh in zip(weights, self.seg_shapes)]
+
+
+def _run_volume(inputs: torch.Tensor, geo: _Geometry, c: _Call, buffer):
+    """Every window of the (padded, contiguous) volume `inputs` through the predictor into the all-window logits, one blend per image and output, the padding
+    cropped (utils.py:300-313), the result on `c.out_device`: the packed outputs.  `buffer`: (axis, steps) for the reference's buffered summation order, else None.
+    Raises `_LogitsDoNotFit` -- before the predictor is called wherever its `out_channels` is known."""
+    num_spatial_dims, roi_size, roi3, grid3, num_win = len(geo.roi_size), geo.roi_size, geo.roi3, geo.grid3, geo.num_win
+    batch_size, in_ch = inputs.shape[:2]
+    dtype, dev = inputs.dtype, inputs.device
 
     # windows owned by this rank: all of them, or (window sharding on) its slot of every round -- monai_amd/parallel.py
     shard = parallel.window_shard(num_win)
-    nb = _auto_batch(predictor, roi3, num_win, sw_batch_size, dev, world=shard.world, sharded=shard.sharded)
+    nb = _auto_batch(c.predictor, roi3, num_win, c.sw_batch_size, dev, world=shard.world, sharded=shard.sharded)
     nb = shard.agree_batch(nb, dev)
     my_rounds = shard.rounds(nb)
-    fused = hasattr(predictor, "forward_into") and not with_coord and not args and not kwargs and process_fn is None
-    win_buf = torch.empty((nb, in_ch) + roi3, dtype=compute_dtype, device=dev)
-
-    windows_nd = None
-    if with_coord:
-        import itertools
-
-        windows_nd = [tuple(slice(s, s + roi_size[d]) for d, s in enumerate(w)) for w in itertools.product(*starts)]
-
-    mosaic = None      # fused single-GPU path: the logits in the mosaic layout (ops.LogitsMosaic) instead of window-major rows
-    logits = None      # per output: [num_win_padded, K, *seg3]
-    seg_shapes = None  # per output: spatial shape of one window's prediction (native dims)
-    dict_keys = None
-    outputs = None     # per output: [B, K, *out_img3]
-    weights = None     # per output: importance map resampled to the prediction size (device)
-    proc_weights = None  # process_fn: per output, the first batch's weight map (the reference's count map uses only that one)
-    imp_dev = None
-    zscales = None
-
-    fused = fused and hasattr(predictor, "out_channels") and getattr(predictor, "window_sized_output", True)
     # buffer_steps with a callback in the loop: the predictor sees the reference's buffered batch schedule (sorted windows, batches cut at the slab ends)
-    buffered_calls = buffered and not fused and (process_fn is not None or with_coord or not shard.sharded)
+    buffered_calls = buffer is not None and not c.fused and (c.process_fn is not None or c.with_coord or not shard.sharded)
     if buffered_calls and shard.sharded:
         raise NotImplementedError("monai_amd: buffer_steps with process_fn / with_coord under window sharding is not on the HIP path")
+    win_buf = torch.empty((int(c.sw_batch_size) if buffered_calls else nb, in_ch) + roi3, dtype=dtype, device=dev)
+    windows_nd = [tuple(slice(s, s + r) for s, r in zip(w, roi_size)) for w in itertools.product(*geo.starts)] if c.with_coord else None
+
+    def predict(b, n, runs):      # the first `n` windows of win_buf, which hold the rows `runs` of image `b`
+        coords = [[slice(b, b + 1), slice(None), *windows_nd[r]] for r0, cnt in runs for r in range(r0, r0 + cnt)] if c.with_coord else None
+        return logits.predict(win_buf[:n].reshape((n, in_ch) + roi_size), coords, runs)
+
+    logits = _WindowLogits(c, geo, shard, nb, buffer, buffered_calls, dtype, dev)
+    if hasattr(c.predictor, "out_channels") and (c.fused or buffered_calls):
+        # sized from the engine's out_channels, not from a first prediction: a rank whose slot of the first round is empty allocates too
+        logits.open([int(c.predictor.out_channels)], [roi_size])
+    outputs = None     # per output: [B, K, *out_img3]
+    weights = None     # per output: importance map resampled to the prediction size (device)
     for b in range(batch_size):
-        vol3 = inputs[b].reshape((in_ch,) + img3)
+        vol3 = inputs[b].reshape((in_ch,) + geo.img3)
         steps = list(enumerate(my_rounds))
-        if progress:
+        if c.progress:
             try:
                 from tqdm import tqdm
 
@@ -318,171 +424,107 @@ def sliding_window_inference(
         pending = []
         if buffered_calls:
             steps = []            # the windows of this image are predicted here, in the reference's buffered order; the blend below reads their rows
-            keys_b, logits, count_map = _buffered_batches(b, vol3, in_ch, grid3, starts, roi_size, roi3, num_win, int(sw_batch_size), predictor, process_fn, with_coord,
-                                                          imp, buffer_dim, int(buffer_steps), shard, nb, compute_dtype, dev, args, kwargs, logits)
-            if b == 0:
-                dict_keys = keys_b
-                seg_shapes, zscales = [tuple(roi_size)], [None]
-                if count_map is not None:
-                    proc_weights = [count_map]
+            first_flush = _buffered_batches(vol3, geo, int(c.sw_batch_size), buffer, win_buf, lambda n, runs: predict(b, n, runs))
+            if b == 0 and first_flush:
+                logits.count_from(first_flush)
         for q, (w0, n) in steps:
-            if fused and logits is None:       # sized from the engine's out_channels, not from a first prediction: a rank whose slot of the first round is empty allocates too
-                k = int(predictor.out_channels)
-                seg_shapes, zscales = [tuple(roi_size)], [None]
-                mosaic = None if buffered else _alloc_mosaic(predictor, shard, argmax_dtype, k, grid3, roi3, compute_dtype, dev)
-                logits = [mosaic if mosaic is not None else _alloc_logits(shard, nb, k, roi3, compute_dtype, dev)]
-            if n > 0 and fused:
+            if n > 0:
                 ops.window_extract(vol3, grid3, w0, n, roi3, win_buf[:n])
+            if n > 0 and c.fused:
                 with _prof.span("sw_predictor"):
-                    if mosaic is not None:     # the network's last kernel writes the windows straight into the mosaic layout
-                        predictor.forward_into_windows(win_buf[:n], mosaic, w0)
+                    if isinstance(logits.stores[0], ops.LogitsMosaic):     # the network's last kernel writes the windows straight into the mosaic layout
+                        c.predictor.forward_into_windows(win_buf[:n], logits.stores[0], w0)
                     else:
-                        predictor.forward_into(win_buf[:n], logits[0][w0 : w0 + n])
+                        c.predictor.forward_into(win_buf[:n], logits.stores[0][w0 : w0 + n])
             elif n > 0:
-                ops.window_extract(vol3, grid3, w0, n, roi3, win_buf[:n])
-                win_data = win_buf[:n].reshape((n, in_ch) + tuple(roi_size))
-                if with_coord:
-                    coords = [[slice(b, b + 1), slice(None)] + list(windows_nd[i]) for i in range(w0, w0 + n)]
-                    seg_out = predictor(win_data, coords, *args, **kwargs)
-                else:
-                    seg_out = predictor(win_data, *args, **kwargs)
-                dict_keys, segs = _flatten_struct(seg_out)
-                w_batch = None
-                if process_fn is not None:     # utils.py:232-238: the callback may edit the predictions and the weight map
-                    if imp_dev is None:
-                        imp_dev = imp.to(dev)
-                    segs, w_t = process_fn(segs, win_data, imp_dev)
-                    segs = tuple(segs) if isinstance(segs, (list, tuple)) else (segs,)
-                    if w_t.dim() == num_spatial_dims:
-                        w_t = w_t[None, None]
-                    w_batch = w_t.to(dtype=compute_dtype, device=dev)
-                if buffered and logits is None and (len(segs) != 1 or tuple(segs[0].shape[2:]) != tuple(roi_size)):
-                    # known after the FIRST batch, not after all of them (the reference ignores further outputs there and fails on a resized one)
-                    raise NotImplementedError("monai_amd: buffer_steps with several / multi-resolution predictor outputs is not on the HIP path")
-                if logits is None:
-                    seg_shapes = [tuple(s.shape[2:]) for s in segs]
-                    zscales = [
-                        None if sh == tuple(roi_size) else [o / float(i) for o, i in zip(sh, roi_size)] for sh in seg_shapes
-                    ]
-                    logits = [_alloc_logits(shard, nb, int(s.shape[1]), _to3(sh, 1), compute_dtype, dev) for s, sh in zip(segs, seg_shapes)]
-                for ss, s in enumerate(segs):
-                    if s.dtype != compute_dtype and s.is_floating_point():
-                        # a predictor under torch.autocast returns half precision; the reference weights it in that precision and
-                        # accumulates in compute_dtype (utils.py:286-288) -- here it is widened first (never less precise)
-                        s = s.to(compute_dtype)
-                    _lib.require_device(s)
-                    dst = logits[ss][w0 : w0 + n]
-                    if w_batch is None:
-                        dst.copy_(s.reshape(dst.shape))
-                        continue
-                    if zscales[ss] is not None:      # cumulative nearest resampling, as utils.py:260-263
-                        w_batch = F.interpolate(w_batch, seg_shapes[ss], mode=_NEAREST)
-                    if w_batch.shape[0] != 1 or w_batch.shape[1] != 1:
-                        raise RuntimeError("monai_amd: process_fn must return a weight map broadcastable over batch and channels "
-                                           f"(got {tuple(w_batch.shape)}; the reference's count map needs [1, 1, *spatial])")
-                    if proc_weights is None:
-                        proc_weights = []
-                    if len(proc_weights) <= ss:      # the count map is built from the FIRST batch's map (utils.py:270-275)
-                        proc_weights.append(w_batch[0, 0].reshape(_to3(seg_shapes[ss], 1)).contiguous().clone())
-                    torch.mul(s.reshape(dst.shape), w_batch.reshape((1, 1) + tuple(dst.shape[2:])), out=dst)   # `seg *= w_t`
+                first_batch = predict(b, n, [(w0, n)])
+                if first_batch and logits.proc_weights is None:
+                    logits.count_from(first_batch)
             if shard.sharded:
-                if logits is None:
+                if logits.stores is None:
                     raise RuntimeError("monai_amd: a rank without windows in the first round cannot size the logits buffer "
                                        "(fewer windows than ranks x windows per launch: lower sw_batch_size)")
                 # this round's rows travel while the next round computes
-                pending += [shard.gather_round(lg, q, nb) for lg in logits]
+                pending += [shard.gather_round(lg, q, nb) for lg in logits.stores]
 
-        if logits is None:
+        if logits.stores is None:
             raise RuntimeError("monai_amd: no windows were processed")
         with _prof.span("sw_gather_wait"):         # what the compute stream still has to wait for after its last round
             for work in pending:
                 work.wait()
-        gathered = logits
 
         if weights is None:  # importance map per output resolution (the reference resamples cumulatively, utils.py:260-263)
-            weights, w_t = [], imp[None, None]
-            for sh, z in zip(seg_shapes, zscales):
+            weights, w_t = [], c.imp[None, None]
+            for sh, z in zip(logits.seg_shapes, logits.zscales):
                 if z is not None:
                     w_t = F.interpolate(w_t, sh, mode=_NEAREST)
-                weights.append(_on_device(w_t[0, 0].reshape(_to3(sh, 1)).contiguous(), dev, cache_key=None if imp_key is None else imp_key + (tuple(sh),)))
+                weights.append(_on_device(w_t[0, 0].reshape(_to3(sh, 1)).contiguous(), dev, cache_key=None if c.imp_key is None else c.imp_key + (tuple(sh),)))
             outputs = []
-            for lg, z in zip(gathered, zscales):
-                osz = [int(i * zz) for i, zz in zip(image_size, z)] if z else list(image_size)
-                if argmax_dtype is not None:       # only the label map is ever written: [B, 1, ...]
-                    outputs.append(torch.empty((batch_size, 1) + _to3(osz, 1), dtype=argmax_dtype, device=dev))
+            for lg, z in zip(logits.stores, logits.zscales):
+                osz = [int(i * zz) for i, zz in zip(geo.image_size, z)] if z else list(geo.image_size)
+                # with the fused argmax only the label map is ever written: [B, 1, ...]
+                k_out, dtype_out = (1, c.argmax_dtype) if c.argmax_dtype is not None else (_channels(lg), dtype)
+                outputs.append(torch.empty((batch_size, k_out) + _to3(osz, 1), dtype=dtype_out, device=dev))
+        for ss, (lg, z) in enumerate(zip(logits.stores, logits.zscales)):
+            g = grid3 if z is None else [[0]] * (3 - num_spatial_dims) + [[int(s * zz) for s in ax] for ax, zz in zip(geo.starts, z)]
+            out = outputs[ss][b]
+            nlog = num_win * _channels(lg) * math.prod(_to3(logits.seg_shapes[ss], 1))
+            with _prof.span("sw_blend", 4.0 * nlog + out.numel() * out.element_size()):      # logits read once + output written once
+                if logits.proc_weights is not None:
+                    w = logits.proc_weights[ss]
+                elif isinstance(lg, ops.LogitsMosaic) and c.imp_key is not None:
+                    w = _factored_map(c.imp_key, c.imp, roi3, c.mode, c.sigma_scale, dev)
                 else:
-                    outputs.append(torch.empty((batch_size, lg.k if lg is mosaic else lg.shape[1]) + _to3(osz, 1), dtype=compute_dtype, device=dev))
-        for ss, (lg, z) in enumerate(zip(gathered, zscales)):
-            if z is None:
-                g = grid3
-            else:
-                g = [[0]] * (3 - num_spatial_dims) + [[int(s * zz) for s in ax] for ax, zz in zip(starts, z)]
-            nlog = num_win * lg.k * roi3[0] * roi3[1] * roi3[2] if lg is mosaic else lg[:num_win].numel()
-            nbytes = 4.0 * nlog + outputs[ss][b].numel() * outputs[ss][b].element_size()  # logits read once + output written once
-            with _prof.span("sw_blend", nbytes):
-                if buffered:      # the reference's buffered summation order (single output at window resolution; checked after the first predictor batch)
-                    ops.sw_blend_buffered(lg[:num_win], proc_weights[ss] if proc_weights is not None else weights[ss], outputs[ss][b], g, _to3(seg_shapes[ss], 1),
-                                          buffer_dim + (3 - num_spatial_dims), int(buffer_steps), premultiplied=proc_weights is not None)
-                elif lg is mosaic:
-                    ops.sw_blend_mosaic(mosaic, _factored_map(imp_key, imp, roi3, mode, sigma_scale, dev) if imp_key is not None else weights[ss], outputs[ss][b])
-                elif argmax_dtype is not None:
-                    _blend_argmax(lg[:num_win], proc_weights[ss] if proc_weights is not None else weights[ss], outputs[ss][b, 0], g,
-                                  _to3(seg_shapes[ss], 1), premultiplied=proc_weights is not None)
-                elif proc_weights is not None:
-                    ops.sw_blend(lg[:num_win], proc_weights[ss], outputs[ss][b], g, _to3(seg_shapes[ss], 1), premultiplied=True)
-                else:
-                    ops.sw_blend(lg[:num_win], weights[ss], outputs[ss][b], g, _to3(seg_shapes[ss], 1))
+                    w = weights[ss]
+                _blend(lg, w, out, geo, g, _to3(logits.seg_shapes[ss], 1), buffer, c.argmax_dtype is not None, logits.proc_weights is not None)
 
     # back to the caller's rank / crop the padding (utils.py:300-313) / output device
     finals = []
-    for ss, o in enumerate(outputs):
-        z = zscales[ss]
-        osz = [int(i * zz) for i, zz in zip(image_size, z)] if z else list(image_size)
+    for o, z in zip(outputs, logits.zscales):
+        osz = [int(i * zz) for i, zz in zip(geo.image_size, z)] if z else list(geo.image_size)
         o = o.reshape((batch_size, o.shape[1]) + tuple(osz))
-        if any(pad_size):
+        if any(geo.pad_size):
             zoom = [sd / float(rd) for sd, rd in zip(o.shape[2:], roi_size)]
             cut = []
             for sp in range(num_spatial_dims):
                 si = num_spatial_dims - sp - 1
-                cut.insert(0, slice(int(round(pad_size[sp * 2] * zoom[si])), int(round((pad_size[sp * 2] + image_size_[si]) * zoom[si]))))
+                cut.insert(0, slice(int(round(geo.pad_size[sp * 2] * zoom[si])), int(round((geo.pad_size[sp * 2] + geo.spatial[si]) * zoom[si]))))
             o = o[(slice(None), slice(None), *cut)]
-        if o.device != out_device:
-            o = o.to(out_device)
-        if meta_src is not None:
-            o = _restore_meta(o, meta_src)
-        finals.append(o)
-    if any(pad_size):
-        kwargs.update({"pad_size": pad_size})
-    return _pack_struct(finals, dict_keys)
+        finals.append(o if o.device == c.out_device else o.to(c.out_device))
+    return _pack_struct(finals, logits.dict_keys)
 
 
-def _buffered_batches(b, vol3, in_ch, grid3, starts, roi_size, roi3, num_win, sw_batch_size, predictor, process_fn, with_coord, imp, buffer_dim, buffer_steps,
-                      shard, nb, dtype, dev, args, kwargs, logits):
-    """The predictor calls of the reference's buffered schedule for image `b` (monai/inferers/utils.py:215-253 with `_create_buffered_slices`, :324-348): windows
-    stably sorted by their start along `buffer_dim`; flush boundaries after every min(#distinct starts, buffer_steps) distinct starts; batches of `sw_batch_size`
-    sorted windows that END at a boundary; `with_coord` hands over the sorted slices; only the first of several outputs is kept (utils.py:244).  Every window's
-    (weighted, when a `process_fn` returned the map) prediction goes to row = its row-major index of ONE all-window buffer: `mh_sw_blend_buffered_f32` then sums in
-    the buffered order.  -> (dict keys of the predictor's output or None, [logits], the count's weight map or None = the importance map)."""
-    import itertools
+def _blend(store, weight, out, geo: _Geometry, grid, seg3, buffer, argmax: bool, premultiplied: bool) -> None:
+    """The one blend launch of an output of an image (`out` [K or 1, *img3]): the reference's buffered summation order (single output at window resolution), the
+    mosaic layout, the fused argmax epilogue, or the plain blend.  premultiplied: a process_fn's weights are already in the rows; `weight` feeds the count only."""
+    if buffer is not None:
+        ops.sw_blend_buffered(store[: geo.num_win], weight, out, grid, seg3, buffer[0] + 3 - len(geo.roi_size), buffer[1], premultiplied=premultiplied)
+    elif isinstance(store, ops.LogitsMosaic):
+        ops.sw_blend_mosaic(store, weight, out)
+    elif argmax:
+        _blend_argmax(store[: geo.num_win], weight, out[0], grid, seg3, premultiplied=premultiplied)
+    else:
+        ops.sw_blend(store[: geo.num_win], weight, out, grid, seg3, premultiplied=premultiplied)
 
+
+def _buffered_batches(vol3, geo: _Geometry, sw_batch_size: int, buffer, win_buf, predict) -> list:
+    """The predictor calls of the reference's buffered schedule for one image (monai/inferers/utils.py:215-253 with `_create_buffered_slices`, :324-348): windows
+    stably sorted by their start along the buffer axis; flush boundaries after every min(#distinct starts, buffer_steps) distinct starts; batches of `sw_batch_size`
+    sorted windows that END at a boundary, gathered into `win_buf` and handed to `predict(count, runs)`.  Every window's prediction goes to row = its row-major index
+    of ONE all-window buffer: `mh_sw_blend_buffered_f32` then sums in the buffered order.  -> what `predict` returned for the last batch of the FIRST flush: the
+    reference builds its count map then."""
     import numpy as np
 
-    nsp = len(roi_size)
-    wins = np.asarray(list(itertools.product(*[range(len(s)) for s in starts])), dtype=np.int64)             # [num_win, nsp] per-axis window numbers, row-major
-    start_along = np.asarray(starts[buffer_dim], dtype=np.int64)[wins[:, buffer_dim]]
+    buffer_dim, buffer_steps = buffer
+    wins = np.asarray(list(itertools.product(*[range(len(s)) for s in geo.starts])), dtype=np.int64)             # [num_win, nsp] per-axis window numbers, row-major
+    start_along = np.asarray(geo.starts[buffer_dim], dtype=np.int64)[wins[:, buffer_dim]]
     order = np.argsort(start_along, kind="mergesort")
     _, counts = np.unique(start_along[order], return_counts=True)
     b_ends = np.cumsum(counts).tolist()
     x = [0, *b_ends][:: min(len(b_ends), buffer_steps)]
     if x[-1] < b_ends[-1]:
         x.append(b_ends[-1])
-    win_buf = torch.empty((sw_batch_size, in_ch) + tuple(roi3), dtype=dtype, device=dev)
-    imp_dev = imp.to(dev)
-    dict_keys, count_map = None, None
-    if logits is None and hasattr(predictor, "out_channels"):
-        # the fit decision BEFORE any predictor call where the class count is known: a stateful predictor / process_fn must not see a batch twice because the
-        # all-window buffer turned out not to fit after the first one (the caller then retries in the plain order)
-        logits = [_alloc_logits(shard, nb, int(predictor.out_channels), roi3, dtype, dev)]
+    first_flush = []
     for gi in range(len(x) - 1):
         for g0 in range(x[gi], x[gi + 1], sw_batch_size):
             idx = [int(order[i]) for i in range(g0, min(g0 + sw_batch_size, x[gi + 1]))]
@@ -491,43 +533,12 @@ def _buffered_batches(b, vol3, in_ch, grid3, starts, roi_size, roi3, num_win, sw
                 run = 1
                 while k + run < len(idx) and idx[k + run] == idx[k] + run:
                     run += 1
-                ops.window_extract(vol3, grid3, idx[k], run, roi3, win_buf[k : k + run])
+                ops.window_extract(vol3, geo.grid3, idx[k], run, geo.roi3, win_buf[k : k + run])
                 k += run
-            win_data = win_buf[: len(idx)].reshape((len(idx), in_ch) + tuple(roi_size))
-            if with_coord:
-                coords = [[slice(b, b + 1), slice(None)] + [slice(int(starts[d][wins[w, d]]), int(starts[d][wins[w, d]]) + int(roi_size[d])) for d in range(nsp)] for w in idx]
-                seg_out = predictor(win_data, coords, *args, **kwargs)
-            else:
-                seg_out = predictor(win_data, *args, **kwargs)
-            dict_keys, segs = _flatten_struct(seg_out)
-            w_t = None
-            if process_fn is not None:
-                segs, w_t = process_fn(segs, win_data, imp_dev)
-                segs = tuple(segs) if isinstance(segs, (list, tuple)) else (segs,)
-                if w_t.dim() == nsp:
-                    w_t = w_t[None, None]
-                w_t = w_t.to(dtype=dtype, device=dev)
-            seg = segs[0]
-            if tuple(seg.shape[2:]) != tuple(roi_size):
-                raise NotImplementedError("monai_amd: buffer_steps with a predictor whose output is not window-sized is not on the HIP path (the reference fails there too)")
-            if seg.dtype != dtype and seg.is_floating_point():
-                seg = seg.to(dtype)
-            _lib.require_device(seg)
-            if logits is None:
-                logits = [_alloc_logits(shard, nb, int(seg.shape[1]), roi3, dtype, dev)]
-            elif int(seg.shape[1]) != int(logits[0].shape[1]):
-                raise RuntimeError(f"monai_amd: the predictor returned {int(seg.shape[1])} channels, its `out_channels` says {int(logits[0].shape[1])}")
-            for k, w in enumerate(idx):
-                dst = logits[0][w]
-                if w_t is None:
-                    dst.copy_(seg[k].reshape(dst.shape))
-                else:
-                    torch.mul(seg[k].reshape(dst.shape), w_t[0 if w_t.shape[0] == 1 else k].reshape((-1,) + tuple(dst.shape[1:])), out=dst)      # `p * w_t`
-        if gi == 0 and b == 0 and process_fn is not None:
-            count_map = w_t[0, 0].reshape(tuple(roi3)).contiguous().clone()          # the count map is built at the FIRST flush from the map current then (utils.py:264-275)
-    if dict_keys is not None:
-        dict_keys = dict_keys[:1]
-    return dict_keys, logits, count_map
+            last = predict(len(idx), [(w, 1) for w in idx])
+        if gi == 0:
+            first_flush = last
+    return first_flush
 
 
 # ---- importance maps: host evaluation and upload happen once per (patch size, mode, sigma, dtype), not once per call -------------------------
@@ -609,6 +620,20 @@ def _window_stride(dense: int) -> int:
     return dense + pad_bytes // 4
 
 
+def _check_fit(need, shard, dev) -> None:
+    """The fit rule of the all-window logits, either layout: at most 90 % of the free HBM and at most the explicit cap (`_logits_budget`).  The decision must be
+    the same on every rank (a rank that went slab-wise alone would dead-lock the others' collectives): under window sharding the free memory is the MINIMUM over
+    the ranks (`agree_batch`; the identity, and no collective, when the call is not sharded)."""
+    if dev.type == "cuda":
+        free, _ = torch.cuda.mem_get_info(dev)
+        free = float(shard.agree_batch(int(free), dev))
+        if need > 0.9 * free:
+            raise _LogitsDoNotFit(need, free)
+    limit = _logits_budget(dev)
+    if limit is not None and need > limit:
+        raise _LogitsDoNotFit(need, limit)
+
+
 def _alloc_logits(shard, nb: int, k: int, seg3, dtype, dev) -> torch.Tensor:
     """Logits of every window of the image, [num_win (padded to whole rounds when sharded), K, *seg3] as a view of one flat
     buffer with a padded window stride (`_window_stride`): the predictor writes its windows' rows, window sharding completes
@@ -616,17 +641,7 @@ def _alloc_logits(shard, nb: int, k: int, seg3, dtype, dev) -> torch.Tensor:
     rows = shard.padded_windows(nb)
     dense = k * seg3[0] * seg3[1] * seg3[2]
     ws = _window_stride(dense)
-    need = rows * ws * 4
-    # the fit decision must be the same on every rank (a rank that went slab-wise alone would dead-lock the others' collectives):
-    # under window sharding the budget is the MINIMUM over the ranks
-    limit = _logits_budget(dev)
-    if dev.type == "cuda":
-        free, _ = torch.cuda.mem_get_info(dev)
-        free = float(shard.agree_batch(int(free), dev))
-        if need > 0.9 * free:
-            raise _LogitsDoNotFit(need, free)
-    if limit is not None and need > limit:
-        raise _LogitsDoNotFit(need, limit)
+    _check_fit(rows * ws * 4, shard, dev)
     flat = torch.empty(rows * ws, dtype=dtype, device=dev)
     return flat.as_strided((rows, k) + tuple(seg3), (ws, seg3[0] * seg3[1] * seg3[2], seg3[1] * seg3[2], seg3[2], 1))
 
@@ -635,19 +650,12 @@ def _alloc_mosaic(predictor, shard, argmax_dtype, k: int, grid3, roi3, dtype, de
     """The mosaic logits layout (ops.LogitsMosaic: the windows of one residue class per axis as dense arrays, so the blend reads long runs instead of
     384-byte pieces of 8 ... 27 x K window blocks) when the path allows it: a predictor whose last kernel can write it (`forward_into_windows`), one GPU
     (window sharding gathers window-major rows), the plain blend (the fused-argmax epilogue reads window-major), a regular grid with <= 4 residue
-    classes, K <= 8.  Same result bits either way; MONAI_AMD_LOGITS_LAYOUT=windows keeps the window-major buffer.  The same fit rule as _alloc_logits."""
+    classes, K <= 8.  Same result bits either way; MONAI_AMD_LOGITS_LAYOUT=windows keeps the window-major buffer."""
     if (not hasattr(predictor, "forward_into_windows") or shard.sharded or argmax_dtype is not None or dtype != torch.float32
             or os.environ.get("MONAI_AMD_LOGITS_LAYOUT") == "windows" or not ops.LogitsMosaic.supported(grid3, roi3, k)):
         return None
     layout = ops.LogitsMosaic(grid3, roi3, k, dev, dtype, allocate=False)
-    need = 4.0 * layout.total
-    limit = _logits_budget(dev)
-    if dev.type == "cuda":
-        free, _ = torch.cuda.mem_get_info(dev)
-        if need > 0.9 * free:
-            raise _LogitsDoNotFit(need, float(free))
-    if limit is not None and need > limit:
-        raise _LogitsDoNotFit(need, limit)
+    _check_fit(4.0 * layout.total, shard, dev)
     return layout.allocate()
 
 
