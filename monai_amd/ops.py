@@ -888,7 +888,8 @@ def crop_pad(src: torch.Tensor, start: Sequence[int], size: Sequence[int], value
 
 def groupnorm_finalize(stats, tiles: int, n: int, c: int, groups: int, gamma, beta, eps: float, slope: float, nrm: torch.Tensor):
     """GroupNorm flavour of `instnorm_finalize`: the records of the C / groups channels of a group are merged; every channel
-    gets {alpha = gamma_c / sqrt(var_g + eps), beta = beta_c - mean_g * alpha, slope, 0}."""
+    gets {alpha = gamma_c / sqrt(var_g + eps), beta = beta_c - mean_g * alpha, slope, bound}; bound = (|gamma_c| sqrt(count_g) + |beta_c|) max(1, |slope|)
+    with count_g the group's element count -- the magnitude bound `instnorm_finalize` writes, never below max |act(x)| of the channel."""
     _lib.require_device(stats, gamma, beta, nrm)
     if nrm.dim() != 3 or nrm.shape[2] != 4 or nrm.stride(2) != 1 or nrm.stride(1) != 4:
         raise RuntimeError("monai_amd.groupnorm_finalize: nrm must be a [N,C,4] slice")

@@ -1008,3 +1008,373 @@ def case_sw_blend_mosaic(device):
     assert not ops.LogitsMosaic.supported([[0, 1, 3, 5], [0, 6], [0, 4, 12]], (4, 6, 8), 3)            # irregular starts
     assert not ops.LogitsMosaic.supported([[0, 2, 4, 6, 7], [0], [0]], (16, 8, 8), 3)                   # step 2, roi 16: more than 4 classes
     assert not ops.LogitsMosaic.supported([[0], [0], [0, 6, 10]], (8, 8, 10), 3)                        # x extents not divisible by 4
+
+
+# ------------------------------------------------------------------------------------------ plain (VALU) network kernels, each against float64
+def _worst(worst, key, err, tol):
+    """keep the largest error / tolerance ratio seen under `key` (the cases return these for the test's -s output)"""
+    if key not in worst or err / tol > worst[key][0] / worst[key][1]:
+        worst[key] = (err, tol)
+    return worst
+
+
+def case_conv3d_strided3(device):
+    """ops.conv3d_k3_strided3 (one stride per axis: the anisotropic nnU-Net plans, kernels/nn_simple.h conv3d_k3_strided_kernel) against F.conv3d in float64: stride 3,
+    extent-1 axes, the exact-width pass (Cout <= 8), a full and a ragged group of 16, output into a channel slice; the shape rule out = (in - 1) // s + 1"""
+    gen = torch.Generator().manual_seed(81)
+    n, worst = 2, {}
+    for strides, dims in (((1, 2, 2), (3, 5, 7)), ((2, 2, 1), (5, 4, 1)), ((2, 1, 2), (1, 9, 6)), ((3, 2, 1), (7, 7, 3)), ((2, 2, 2), (1, 1, 1))):
+        odims = tuple((d - 1) // s + 1 for d, s in zip(dims, strides))
+        for cin in (2, 3, 4):
+            x = torch.randn((n, cin) + dims, generator=gen)
+            nrm = _rand_nrm(n, cin, gen)
+            xa = _act(x.double(), nrm.double())
+            for cout in (5, 9, 16, 19):
+                w = torch.randn((cout, cin, 3, 3, 3), generator=gen) * 0.1
+                b = torch.randn(cout, generator=gen) * 0.1
+                packed = ops.conv3d_k3_pack(0, w.to(device))
+                for bias in (b, None):
+                    exp = F.conv3d(xa, w.double(), None if bias is None else bias.double(), stride=strides, padding=1)
+                    assert tuple(exp.shape[2:]) == odims, (strides, dims)
+                    buf = torch.full((n, cout + 4) + odims, float("nan"), device=device)
+                    ops.conv3d_k3_strided3(x.to(device), nrm.to(device), packed, None if bias is None else bias.to(device), buf[:, 4:], strides)
+                    got = buf.cpu()
+                    err = (got[:, 4:].double() - exp).abs().max().item()      # NaN (an unwritten voxel) fails the comparison
+                    assert err < 2e-5, f"conv3d_k3_strided3 {strides} {dims} {cin}->{cout} bias={bias is not None}: max err {err}"
+                    assert torch.isnan(got[:, :4]).all(), "conv3d_k3_strided3 wrote outside its channel slice"
+                    _worst(worst, "conv3d_k3_strided3", err, 2e-5)
+    # the shape rule is the launcher's: floor(in / s) (what a padding-0 rule would give) is refused
+    x = torch.randn((n, 2, 3, 5, 7), generator=gen)
+    packed = ops.conv3d_k3_pack(0, torch.randn((5, 2, 3, 3, 3), generator=gen).to(device))
+    for bad in ((3, 2, 3), (3, 3, 3), (2, 3, 4), (3, 3, 5)):
+        with pytest.raises(RuntimeError):
+            ops.conv3d_k3_strided3(x.to(device), None, packed, None, torch.empty((n, 5) + bad, device=device), (1, 2, 2))
+    return worst
+
+
+def case_deconv_ks(device):
+    """ops.deconv_ks (kernel == stride == factors, each 1 or 2: kernels/nn_simple.h deconv_ks_kernel) for all eight factor triples against F.conv_transpose3d in float64,
+    into the first channels of a wider buffer, a ragged and a full group of 8 output channels, a row longer than a wave whose volume ends inside a workgroup; the
+    records of the slice are {1, 0, 1, max |value written| of the channel} exactly and nothing outside the slice is touched"""
+    gen = torch.Generator().manual_seed(82)
+    n, cin, extra, worst = 2, 5, 3, {}
+    runs = [(f, (3, 5, 7)) for f in itertools.product((1, 2), repeat=3)] + [((2, 2, 2), (1, 1, 70)), ((1, 2, 2), (1, 1, 70))]
+    for f, dims in runs:
+        odims = tuple(a * b for a, b in zip(f, dims))
+        x = torch.randn((n, cin) + dims, generator=gen)
+        nrm = _rand_nrm(n, cin, gen)
+        xa = _act(x.double(), nrm.double())
+        for cout in (11, 8):
+            w = torch.randn((cin, cout) + f, generator=gen) / np.sqrt(cin)
+            b = torch.randn(cout, generator=gen) * 0.1
+            for bias in (b, None):
+                exp = F.conv_transpose3d(xa, w.double(), None if bias is None else bias.double(), stride=f)
+                assert tuple(exp.shape[2:]) == odims
+                cat = torch.full((n, cout + extra) + odims, float("nan"), device=device)
+                rec = torch.full((n, cout + extra, 4), 7.0, device=device)
+                ops.deconv_ks(x.to(device), nrm.to(device), w.to(device), None if bias is None else bias.to(device), cat[:, :cout], f, ops.nrm_identity(rec[:, :cout]))
+                got, r = cat.cpu(), rec.cpu()
+                tol = 1e-5                  # case_deconv's, same kernel class and weight scale
+                err = (got[:, :cout].double() - exp).abs().max().item()
+                assert err < tol, f"deconv_ks {f} {dims} ->{cout} bias={bias is not None}: max err {err}"
+                assert torch.isnan(got[:, cout:]).all() and torch.all(r[:, cout:] == 7.0), f"deconv_ks {f}: channels / records outside the slice touched"
+                assert torch.all(r[:, :cout, 0] == 1) and torch.all(r[:, :cout, 1] == 0) and torch.all(r[:, :cout, 2] == 1)
+                assert torch.equal(r[:, :cout, 3], got[:, :cout].abs().amax(dim=(2, 3, 4))), f"deconv_ks {f}: bound != max |value written| of the channel"
+                _worst(worst, "deconv_ks", err, tol)
+    return worst
+
+
+def case_deconv_k3_strides(device):
+    """ops.deconv_k3 (k3, padding 1, output_padding s - 1) against F.conv_transpose3d in float64: the generic gather kernel at stride 3, the stride-2 kernel's four
+    channel-group variants (<4, false> Cout 3, <5, true> Cout 5, <8, false> Cout 7 / 17, <8, true> Cout 8), dense and into a channel slice, and a stride-2 output
+    that is not 8-byte aligned (the generic kernel again)"""
+    gen = torch.Generator().manual_seed(83)
+    n, cin, worst = 2, 6, {}
+    for stride, dims, couts in ((3, (2, 3, 4), (5, 17)), (2, (3, 3, 5), (3, 5, 7, 8, 17)), (2, (1, 4, 3), (3, 5, 7, 8, 17))):
+        odims = tuple(stride * d for d in dims)
+        ovol = int(np.prod(odims))
+        x = torch.randn((n, cin) + dims, generator=gen)
+        nrm = _rand_nrm(n, cin, gen)
+        xa = _act(x.double(), nrm.double())
+        for cout in couts:
+            w = torch.randn((cin, cout, 3, 3, 3), generator=gen) * 0.1
+            b = torch.randn(cout, generator=gen) * 0.1
+            for bias in (b, None):
+                exp = F.conv_transpose3d(xa, w.double(), None if bias is None else bias.double(), stride=stride, padding=1, output_padding=stride - 1)
+                assert tuple(exp.shape[2:]) == odims
+                args = (x.to(device), nrm.to(device), w.to(device), None if bias is None else bias.to(device))
+                dense = torch.full((n, cout) + odims, float("nan"), device=device)
+                ops.deconv_k3(*args, dense, stride)
+                buf = torch.full((n, cout + 1) + odims, float("nan"), device=device)          # element offset 8 vol (stride 2): still 8-byte aligned
+                ops.deconv_k3(*args, buf[:, 1:], stride)
+                views = [("dense", dense.cpu()), ("slice", buf.cpu()[:, 1:])]
+                assert torch.isnan(buf[:, :1]).all(), "deconv_k3 wrote outside its channel slice"
+                if stride == 2:           # one float into a flat buffer: 4-byte aligned only
+                    flat = torch.full((1 + n * cout * ovol + 1,), float("nan"), device=device)
+                    view = flat.as_strided((n, cout) + odims, (cout * ovol, ovol, odims[1] * odims[2], odims[2], 1), 1)
+                    assert view.data_ptr() % 8 == 4
+                    ops.deconv_k3(*args, view, stride)
+                    fl = flat.cpu()
+                    assert torch.isnan(fl[0]) and torch.isnan(fl[-1]), "deconv_k3 wrote outside its unaligned view"
+                    views.append(("unaligned", fl[1:-1].reshape((n, cout) + odims)))
+                for name, got in views:
+                    err = (got.double() - exp).abs().max().item()
+                    assert err < 2e-5, f"deconv_k3 stride {stride} {dims} ->{cout} bias={bias is not None} ({name}): max err {err}"
+                    _worst(worst, "deconv_k3 stride %d" % stride, err, 2e-5)
+                assert torch.equal(views[0][1], views[1][1]), "deconv_k3: dense and sliced outputs differ"
+    return worst
+
+
+def case_pad_replicate(device):
+    """ops.pad_replicate for all eight growth triples of {0, 1}^3 into a channel slice: bitwise F.pad(mode="replicate") of the RAW values; the input's bounds handed
+    on in identity records; growth of 2 is refused"""
+    gen = torch.Generator().manual_seed(84)
+    n, c, dims = 2, 3, (3, 4, 5)
+    x = torch.randn((n, c) + dims, generator=gen)
+    nb = _with_bounds(x, _rand_nrm(n, c, gen), 3.0)
+    for g in itertools.product((0, 1), repeat=3):
+        odims = tuple(d + v for d, v in zip(dims, g))
+        exp = F.pad(x, (0, g[2], 0, g[1], 0, g[0]), mode="replicate") if any(g) else x
+        out = torch.full((n, c + 2) + odims, float("nan"), device=device)
+        rec = torch.full((n, c + 2, 4), 7.0, device=device)
+        ops.pad_replicate(x.to(device), out[:, 2:], nb.to(device), ops.nrm_identity(rec[:, 2:]))
+        got, r = out.cpu(), rec.cpu()
+        assert torch.equal(got[:, 2:], exp), f"pad_replicate growth {g}"
+        assert torch.isnan(got[:, :2]).all() and torch.all(r[:, :2] == 7.0)
+        assert torch.all(r[:, 2:, 0] == 1) and torch.all(r[:, 2:, 1] == 0) and torch.all(r[:, 2:, 2] == 1) and torch.equal(r[:, 2:, 3], nb[:, :, 3]), f"pad_replicate growth {g}: records"
+        plain = torch.full((n, c) + odims, float("nan"), device=device)          # no records at all
+        ops.pad_replicate(x.to(device), plain)
+        assert torch.equal(plain.cpu(), exp)
+    for axis in range(3):
+        odims = tuple(d + (2 if a == axis else 0) for a, d in enumerate(dims))
+        with pytest.raises(RuntimeError):
+            ops.pad_replicate(x.to(device), torch.empty((n, c) + odims, device=device))
+    return True
+
+
+def case_pixelshuffle(device):
+    """ops.pixelshuffle (kernels/nn_simple.h pixelshuffle_kernel), fz 1 / 2 with and without the pad + average pool: the bare shuffle bitwise its index rule
+    sh[c][fz z + i][2 y + j][2 x + k] = in[c fz 4 + i 4 + j 2 + k][z][y][x]; the pooled form against float64 within 2^-21 max|x| (seven fp32 additions and one division
+    of values no larger than max|x|: 8 roundings of 2^-24 each); the output records max |value written| per (n, c) exactly"""
+    gen = torch.Generator().manual_seed(85)
+    n, c, worst = 2, 3, {}
+    for fz, dims in ((2, (2, 3, 5)), (1, (1, 3, 5)), (2, (2, 3, 70))):
+        d, h, w = dims
+        x = torch.randn((n, c * fz * 4) + dims, generator=gen)
+        x[1] *= 50.0
+        sh = x.reshape(n, c, fz, 2, 2, d, h, w).permute(0, 1, 5, 2, 6, 3, 7, 4).reshape(n, c, fz * d, 2 * h, 2 * w)
+        for pad_pool in (False, True):
+            out = torch.full((n, c, fz * d, 2 * h, 2 * w), float("nan"), device=device)
+            rec = torch.full((n, c + 1, 4), 7.0, device=device)
+            ops.pixelshuffle(x.to(device), out, fz, pad_pool, ops.nrm_identity(rec[:, 1:]))
+            got, r = out.cpu(), rec.cpu()
+            if not pad_pool:
+                assert torch.equal(got, sh), f"pixelshuffle fz={fz} {dims}: not the index rule"
+            else:
+                if fz == 2:
+                    exp = F.avg_pool3d(F.pad(sh.double(), (1, 0, 1, 0, 1, 0)), 2, stride=1)
+                else:         # two spatial dimensions on one plane: nothing in front of, and no pooling over, the plane axis
+                    exp = F.avg_pool3d(F.pad(sh.double(), (1, 0, 1, 0, 0, 0)), (1, 2, 2), stride=1)
+                assert exp.shape == got.shape
+                tol = 2.0 ** -21 * x.abs().max().item()
+                err = (got.double() - exp).abs().max().item()
+                print(f"pixelshuffle fz={fz} {dims} pad_pool: max err {err:.3e} (bound {tol:.3e})")
+                assert err <= tol, f"pixelshuffle fz={fz} {dims} pad_pool: max err {err} > {tol}"
+                _worst(worst, "pixelshuffle pad_pool", err, tol)
+            assert torch.all(r[:, :1] == 7.0) and torch.all(r[:, 1:, 0] == 1) and torch.all(r[:, 1:, 1] == 0) and torch.all(r[:, 1:, 2] == 1)
+            assert torch.equal(r[:, 1:, 3], got.abs().amax(dim=(2, 3, 4))), f"pixelshuffle fz={fz} pad_pool={pad_pool}: bound != max |value written|"
+    return worst
+
+
+def _group_reference(xd, groups, gamma, beta, eps):
+    """float64 {alpha, beta} of a GroupNorm over `groups` groups of xd [N, C, D, H, W], and the group's element count"""
+    n, c = xd.shape[:2]
+    g = xd.reshape(n, groups, -1)
+    mean = g.mean(dim=2).repeat_interleave(c // groups, dim=1)
+    var = g.var(dim=2, unbiased=False).repeat_interleave(c // groups, dim=1)
+    ga = torch.ones(c, dtype=torch.float64) if gamma is None else gamma.double()
+    be = torch.zeros(c, dtype=torch.float64) if beta is None else beta.double()
+    alpha = ga[None] / torch.sqrt(var + eps)
+    return alpha, be[None] - mean * alpha, g.shape[2], ga, be
+
+
+def case_groupnorm_finalize(device):
+    """ops.groupnorm_finalize (kernels/nn_simple.h instnorm_finalize_kernel with G > 1) on the records of ops.instnorm_stats, data with a large mean: groups of 4 / 1 /
+    all channels, more than 64 records per group (several trips of the merge loops), more than 64 channels per group (the second trip of the per-channel loop), one
+    plane -- against float64 with the tolerances of case_conv3d's finalize checks; the bound component; groups == C bitwise instnorm_finalize"""
+    gen = torch.Generator().manual_seed(86)
+    eps, worst = 1e-5, {}
+    # (33, 32, 33): 9 records per channel, 72 per group -- (17, 16, 17) has 2 per channel (16 per group); the 130-channel group is the other one beyond a wave of records
+    shapes = ((12, 3, (5, 7, 9)), (12, 12, (5, 7, 9)), (8, 1, (17, 16, 17)), (130, 1, (2, 3, 5)), (16, 8, (1, 4, 4)), (8, 1, (33, 32, 33)))
+    for ci, (c, groups, dims) in enumerate(shapes):
+        n = 2
+        x = torch.randn((n, c) + dims, generator=gen) * 3 + 20
+        tiles = ops.instnorm_stat_tiles(*dims)
+        stats = torch.full((n, c, tiles, 3), float("nan"), device=device)
+        ops.instnorm_stats(x.to(device), stats)
+        assert torch.all(stats.cpu()[..., 0].sum(-1) == float(np.prod(dims)))
+        gamma = (torch.rand(c, generator=gen) + 0.5) * torch.where(torch.rand(c, generator=gen) > 0.8, -1.0, 1.0)
+        beta = torch.randn(c, generator=gen) * 0.2
+        # (gamma, beta, slope, n, record offset): full / no affine parameters and a gain > 1 / one sample into a slice of a wider record tensor
+        for gm, bt, slope, nn, off in ((gamma, beta, 0.1, n, 0), (None, None, 2.0, n, 0), (gamma, beta, 0.1, 1, 3)):
+            rec = torch.full((nn, c + off, 4), 7.0, device=device)
+            ops.groupnorm_finalize(stats[:nn], tiles, nn, c, groups, None if gm is None else gm.to(device), None if bt is None else bt.to(device), eps, slope, rec[:, off:])
+            r = rec.cpu().double()
+            assert torch.all(r[:, :off] == 7.0)
+            r = r[:, off:]
+            alpha, shift, count, ga, be = _group_reference(x[:nn].double(), groups, gm, bt, eps)
+            ea, eb = (r[:, :, 0] - alpha).abs().max().item(), (r[:, :, 1] - shift).abs().max().item()
+            ta = 1e-5 * alpha.abs().max().item() + 1e-6
+            assert ea < ta, f"groupnorm_finalize C={c} groups={groups} {dims}: alpha err {ea}"
+            assert eb < 2e-5, f"groupnorm_finalize C={c} groups={groups} {dims}: beta err {eb}"
+            _worst(worst, "groupnorm_finalize alpha", ea, ta)
+            _worst(worst, "groupnorm_finalize beta", eb, 2e-5)
+            assert torch.all(r[:, :, 2] == torch.tensor(slope, dtype=torch.float32).double())
+            bound = (ga.abs() * np.sqrt(float(count)) + be.abs()) * max(1.0, abs(slope))
+            assert torch.allclose(r[:, :, 3], bound[None].expand(nn, -1), rtol=1e-6, atol=0.0)
+            assert torch.all(r[:, :, 3] >= _amax(x[:nn].double(), r[:, :, :3])), "groupnorm_finalize: the bound is below what a consumer sees"
+        if groups == c:
+            a = torch.full((n, c, 4), float("nan"), device=device)
+            b = torch.full((n, c, 4), float("nan"), device=device)
+            ops.groupnorm_finalize(stats, tiles, n, c, groups, gamma.to(device), beta.to(device), eps, 0.1, a)
+            ops.instnorm_finalize(stats, tiles, n, c, gamma.to(device), beta.to(device), eps, 0.1, b)
+            assert torch.equal(a.cpu(), b.cpu()), "groupnorm_finalize with one channel per group != instnorm_finalize"
+        if ci == 0:
+            with pytest.raises(RuntimeError):
+                ops.groupnorm_finalize(stats, tiles, n, c, 5, None, None, eps, 0.1, torch.empty((n, c, 4), device=device))
+    return worst
+
+
+def case_maxpool_planar(device):
+    """ops.maxpool2 with out.D == in.D (MaxPool2d(2) of a 2-D network's plane or stack of planes; kernels/nn_simple.h maxpool2_kernel<., 1>): odd W (scalar loads, the
+    last column dropped), even W (paired loads), one plane with odd H -- bitwise F.max_pool3d(x, (1, 2, 2)) without records, within 1e-6 of the pooled activated values
+    with them (fmaf against mul + add, as case_maxpool), the input's bounds handed on"""
+    gen = torch.Generator().manual_seed(87)
+    worst = {}
+    for shape in ((2, 3, 4, 6, 7), (2, 3, 4, 6, 8), (2, 3, 1, 5, 4)):
+        n, c, d, h, w = shape
+        x = torch.randn(shape, generator=gen)
+        oshape = (n, c, d, h // 2, w // 2)
+        out = torch.full(oshape, float("nan"), device=device)
+        ops.maxpool2(x.to(device), None, out)
+        assert torch.equal(out.cpu(), F.max_pool3d(x, (1, 2, 2))), shape
+        nb = _with_bounds(x, _rand_nrm(n, c, gen), 3.0)
+        a, b, s = (nb[:, :, i][:, :, None, None, None] for i in range(3))
+        y = torch.addcmul(b, x, a)
+        exp = F.max_pool3d(torch.where(y > 0, y, y * s), (1, 2, 2))
+        out = torch.full(oshape, float("nan"), device=device)
+        rec = torch.full((n, c, 4), float("nan"), device=device)
+        ops.maxpool2(x.to(device), nb.to(device), out, rec)
+        err = (out.cpu() - exp).abs().max().item()
+        assert err < 1e-6, (shape, err)
+        _worst(worst, "maxpool2 planar", err, 1e-6)
+        r = rec.cpu()
+        assert torch.equal(r[:, :, 3], nb[:, :, 3]) and torch.all(r[:, :, 0] == 1) and torch.all(r[:, :, 1] == 0) and torch.all(r[:, :, 2] == 1)
+        assert torch.all(r[:, :, 3] >= out.cpu().abs().amax(dim=(2, 3, 4)))
+    return worst
+
+
+# ------------------------------------------------------------------------------------------ what the selector returns, launched
+SELECTED_CINS = (1, 3, 8, 16, 32, 48)
+SELECTED_COUTS = (5, 8, 16, 24, 32, 48, 64)
+# (2, 9, 10): a plane of at least 8 x 8 whose W is no multiple of 4 -- the one precondition of the z-marching split kernels' launcher (W % 4) that no other extent here separates from H >= 8
+SELECTED_DIMS = ((1, 8, 8), (1, 9, 12), (1, 4, 16), (1, 32, 8), (2, 4, 16), (3, 8, 12), (2, 16, 16), (3, 5, 7), (4, 4, 4), (5, 6, 6), (2, 8, 32), (24, 8, 16), (2, 9, 10))
+
+
+def _launch_selected(device, cfg, cin, cout, dims, bounded, gen, worst):
+    """one selected configuration on one shape: dense with bias and into a channel slice without, fused statistics, finalize -- case_conv3d's checks at the GPU tolerance
+    of test_conv_mfma_configs"""
+    n, vox = 2, int(np.prod(dims))
+    x = torch.randn((n, cin) + tuple(dims), generator=gen)
+    w = torch.randn((cout, cin, 3, 3, 3), generator=gen) / np.sqrt(27.0 * cin)
+    b = torch.randn(cout, generator=gen) * 0.1
+    nrm = _rand_nrm(n, cin, gen)
+    if bounded:
+        nrm = _with_bounds(x, nrm, float(np.sqrt(vox)))
+    xa = _act(x.double(), nrm.double())
+    packed = ops.conv3d_k3_pack(cfg, w.to(device))
+    tiles = ops.conv3d_k3_stat_tiles(cfg, *dims)
+    gamma = torch.rand(cout, generator=gen) + 0.5
+    beta = torch.randn(cout, generator=gen) * 0.2
+    for bias, lead in ((b, 0), (None, 4)):          # four leading channels keep every volume 16-byte aligned
+        exp = F.conv3d(xa, w.double(), None if bias is None else bias.double(), padding=1)
+        buf = torch.full((n, cout + lead) + tuple(dims), float("nan"), device=device)
+        stats = torch.full((n, cout, tiles, 3), float("nan"), device=device)
+        ops.conv3d_k3(cfg, x.to(device), nrm.to(device), packed, None if bias is None else bias.to(device), buf[:, lead:], stats)
+        what = f"selected cfg {cfg} {cin}->{cout} {dims} bounded={bounded} lead={lead}"
+        full = buf.cpu()
+        assert torch.isnan(full[:, :lead]).all(), what + ": wrote outside its channel slice"
+        got = full[:, lead:].double()
+        tol = 5e-5 * max(1.0, exp.abs().max().item())
+        err = (got - exp).abs().max().item()
+        assert err < tol, what + f": max err {err}"
+        _worst(worst, "conv3d_k3 selected, split precision" if cfg > ops.conv3d_k3_num_configs() and cfg != ops.conv3d_k3_c1_config() else "conv3d_k3 selected, fp32", err, tol)
+        st = stats.cpu().double()
+        assert not torch.isnan(st).any() and torch.all(st[..., 0].sum(-1) == vox), what + ": statistics counts"
+        nrm_out = torch.full((n, cout, 4), float("nan"), device=device)
+        ops.instnorm_finalize(stats, tiles, n, cout, gamma.to(device), beta.to(device), 1e-5, 0.1, nrm_out)
+        mean, var = got.mean(dim=(2, 3, 4)), got.var(dim=(2, 3, 4), unbiased=False)
+        alpha = gamma.double()[None] / torch.sqrt(var + 1e-5)
+        r = nrm_out.cpu().double()
+        assert (r[:, :, 0] - alpha).abs().max().item() < 1e-5 * alpha.abs().max().item() + 1e-6, what
+        assert (r[:, :, 1] - (beta.double()[None] - mean * alpha)).abs().max().item() < 2e-5, what
+        assert torch.all(r[:, :, 2] == torch.tensor(0.1, dtype=torch.float32).double())
+        assert torch.allclose(r[:, :, 3], (gamma.double().abs() * np.sqrt(float(vox)) + beta.double().abs())[None].expand(n, -1), rtol=1e-6)
+        assert torch.all(r[:, :, 3] >= _amax(got, r[:, :, :3])), what
+
+
+def case_conv3d_selected(device):
+    """What mh_conv3d_k3_select returns over a grid of channel counts and small / odd extents (D == 1, the 2-D networks' plane, included), LAUNCHED: every row must be
+    a configuration the launcher's own preconditions admit (host checks on all rows), and one row per distinct (configuration, extents, bounded) is packed, run with
+    fused statistics dense and into a channel slice, and compared with F.conv3d in float64.  The case asserts which families it reached, so a change to the
+    selector cannot silently empty it.  The in-plane Winograd fp32 configuration needs 48^3 and stays with WINO2D_CASES."""
+    from monai_amd import config
+
+    h2, h2c, h2v, h2w, c1 = ops.conv3d_k3_h2_config(), ops.conv3d_k3_h2c_config(), ops.conv3d_k3_h2v_config(), ops.conv3d_k3_h2w_config(), ops.conv3d_k3_c1_config()
+    split, ntile = (h2, h2c, h2v, h2w), ops.conv3d_k3_num_configs()
+    AUTO, H2, FP32 = 0, 3, 4
+    rows = {}
+    with config.conv_algo_scope("auto"):
+        for cin, cout, bounded, algo, dims in itertools.product(SELECTED_CINS, SELECTED_COUTS, (False, True), (AUTO, H2, FP32), SELECTED_DIMS):
+            cfg = ops.conv3d_k3_select(cin, cout, *dims, bounded=bounded, algo=algo)
+            what = f"select({cin}, {cout}, {dims}, bounded={bounded}, algo={algo}) = {cfg}"
+            assert cfg >= 1 and ops.conv3d_k3_accepts(cfg, cin, cout), what
+            assert cfg not in split or (bounded and algo != FP32), what + ": split precision for an input without bounds / the exact family"
+            assert not (algo == H2 and cfg == h2w), what
+            assert ops.conv3d_k3_stat_tiles(cfg, *dims) >= 1, what
+            rows.setdefault((cfg, dims, bounded), (cin, cout))
+    gen = torch.Generator().manual_seed(88)
+    worst = {}
+    for (cfg, dims, bounded), (cin, cout) in rows.items():
+        _launch_selected(device, cfg, cin, cout, dims, bounded, gen, worst)
+    reached = {cfg for cfg, _, _ in rows}
+    planes = {cfg for cfg, dims, _ in rows if dims[0] == 1}
+    tiles = {cfg for cfg in reached if 1 <= cfg < ntile}
+    assert {h2, h2c, h2v, h2w, c1} <= reached, f"families reached: {sorted(reached)}"
+    assert len(tiles) >= 5, f"fp32 tile configurations reached: {sorted(tiles)}"
+    assert {h2, h2c, c1} <= planes and any(1 <= cfg < ntile for cfg in planes), f"configurations reached on one plane: {sorted(planes)}"
+    assert any(cfg == h2w and dims == (24, 8, 16) for cfg, dims, _ in rows)
+    print(f"conv3d_k3 selected: {len(rows)} (configuration, extents, bounded) rows launched twice; configurations {sorted(reached)}, on one plane {sorted(planes)}")
+    return worst
+
+
+def case_conv3d_selected_misaligned(device):
+    """EMULATOR ONLY (a launcher that lost the check would issue misaligned vector stores on a GPU): the small-volume split-precision configuration, selected for
+    (3, 5, 7), launched into a view that is not 16-byte aligned (channel offset 2 of an odd volume) is refused and writes nothing"""
+    from monai_amd import config
+
+    gen = torch.Generator().manual_seed(89)
+    n, cin, cout, dims = 2, 16, 32, (3, 5, 7)
+    with config.conv_algo_scope("auto"):
+        cfg = ops.conv3d_k3_select(cin, cout, *dims, bounded=True)
+    assert cfg == ops.conv3d_k3_h2v_config()
+    x = torch.randn((n, cin) + dims, generator=gen)
+    nrm = _with_bounds(x, _rand_nrm(n, cin, gen), float(np.sqrt(np.prod(dims))))
+    w = torch.randn((cout, cin, 3, 3, 3), generator=gen) / np.sqrt(27.0 * cin)
+    packed = ops.conv3d_k3_pack(cfg, w.to(device))
+    buf = torch.full((n, cout + 2) + dims, float("nan"), device=device)
+    assert buf[:, 2:].data_ptr() % 16 != 0
+    stats = torch.full((n, cout, 1, 3), float("nan"), device=device)
+    with pytest.raises(RuntimeError):
+        ops.conv3d_k3(cfg, x.to(device), nrm.to(device), packed, None, buf[:, 2:], stats)
+    assert torch.isnan(buf).all() and torch.isnan(stats).all()

@@ -366,3 +366,38 @@ def test_conv_h2w_winograd_split(emu, n, cin, cout, dims):
     if n == 1:      # the accumulating and the pooling forms
         kc.case_conv3d_accumulate("cpu", 1, cin, cout, (3, 4, 32), cfg=cfg)
         kc.case_conv3d_pool("cpu", 1, cin, cout, (4, 8, 16), cfg=cfg)
+
+
+# ---- the plain (VALU) network kernels of kernels/nn_simple.h, each against float64 (the -m gpu twins run the same cases at the same shapes)
+def test_conv3d_per_axis_strides(emu):
+    print(kc.case_conv3d_strided3("cpu"))
+
+
+def test_deconv_kernel_equals_stride_all_factor_triples(emu):
+    print(kc.case_deconv_ks("cpu"))
+
+
+def test_deconv_k3_generic_stride_and_channel_group_variants(emu):
+    print(kc.case_deconv_k3_strides("cpu"))
+
+
+def test_pad_replicate_values_and_bounds(emu):
+    assert kc.case_pad_replicate("cpu")
+
+
+def test_pixelshuffle_and_pad_pool(emu):
+    print(kc.case_pixelshuffle("cpu"))
+
+
+def test_groupnorm_finalize(emu):
+    print(kc.case_groupnorm_finalize("cpu"))
+
+
+def test_maxpool_plane_wise(emu):
+    print(kc.case_maxpool_planar("cpu"))
+
+
+def test_conv3d_selected_configurations_launched(emu):
+    """every configuration conv3d_k3_select returns over a grid of channel counts and small / odd extents is one its launcher takes, and computes the convolution"""
+    print(kc.case_conv3d_selected("cpu"))
+    kc.case_conv3d_selected_misaligned("cpu")      # here only: on a GPU a launcher without the check would issue misaligned vector stores

@@ -318,3 +318,38 @@ POOL_CASES = [(2, 32, 32, (4, 16, 16)), (1, 48, 64, (6, 18, 36)), (1, 16, 32, (2
 def test_conv3d_split_precision_pooling_epilogue(n, cin, cout, dims):
     """MaxPool3d(2) out of the producing convolution's epilogue (conv3d_h2.h, POOL): raw maxima / minima, bitwise; the convolution itself untouched"""
     kc.case_conv3d_pool(DEV, n, cin, cout, dims)
+
+
+# ---- the plain (VALU) network kernels of kernels/nn_simple.h, each against float64 (the same cases and shapes as tests/test_kernels_emu.py)
+def test_conv3d_per_axis_strides():
+    print(kc.case_conv3d_strided3(DEV))
+
+
+def test_deconv_kernel_equals_stride_all_factor_triples():
+    print(kc.case_deconv_ks(DEV))
+
+
+def test_deconv_k3_generic_stride_and_channel_group_variants():
+    print(kc.case_deconv_k3_strides(DEV))
+
+
+def test_pad_replicate_values_and_bounds():
+    assert kc.case_pad_replicate(DEV)
+
+
+def test_pixelshuffle_and_pad_pool():
+    print(kc.case_pixelshuffle(DEV))
+
+
+def test_groupnorm_finalize():
+    print(kc.case_groupnorm_finalize(DEV))
+
+
+def test_maxpool_plane_wise():
+    print(kc.case_maxpool_planar(DEV))
+
+
+def test_conv3d_selected_configurations_launched():
+    """every configuration conv3d_k3_select returns over a grid of channel counts and small / odd extents is one its launcher takes, and computes the convolution
+    (the refusal of a misaligned view is checked on the emulator only)"""
+    print(kc.case_conv3d_selected(DEV))
