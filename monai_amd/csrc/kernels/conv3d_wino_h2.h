@@ -90,14 +90,28 @@ __device__ __forceinline__ void hw_split4p(const f32x4 v, const float m1, u32x2&
     lo = u32x2{l0, l1};
 #endif
 }
-// the value of lane ^ 32 (hi = this lane is in the upper half): one v_permlane32_swap_b32 of two copies -- {x.lo, x.lo} and {x.hi, x.hi} -- and a select; no LDS round trip
-__device__ __forceinline__ float hw_xchg32(const float x, const int hi) {
+// a value that is the same in every lane of the wave, held in a scalar register instead of a vector one (the march has no vector register to spare)
+__device__ __forceinline__ float hw_uniform(const float x) {
 #ifdef MH_SIMT_EMULATOR
-    (void)hi;
-    return __shfl_xor(x, 32);
+    return x;
 #else
-    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, x), __builtin_bit_cast(unsigned, x), false, false);
-    return __builtin_bit_cast(float, hi ? r[0] : r[1]);
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
+#endif
+}
+// The pooling exchange of a tile pair: lanes 0-31 (hi = 0) keep the maxima, lanes 32-63 the minima.  `own` = this lane's value of its kind, `rcv` = lane ^ 32's value
+// of the SAME kind: one v_permlane32_swap_b32 of (mx, mn) -- it exchanges the upper half of its first operand with the lower half of its second, so afterwards the
+// first holds {own mx | partner's mn}, the second {partner's mx | own mn}: both halves have their own and their partner's value, in either order (the median of three
+// that follows is symmetric).  No copies, no selects.
+__device__ __forceinline__ void hw_xchg32_pair(const float mx, const float mn, const int hi, float& own, float& rcv) {
+#ifdef MH_SIMT_EMULATOR
+    own = hi ? mn : mx;
+    rcv = __shfl_xor(hi ? mx : mn, 32);
+#else
+    (void)hi;
+    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, mx), __builtin_bit_cast(unsigned, mn), false, false);
+    const unsigned r0 = r[0], r1 = r[1];      // as values first: __builtin_bit_cast of the vector ELEMENT r[1] reads element 0 (hipcc 6.x)
+    own = __builtin_bit_cast(float, r0);
+    rcv = __builtin_bit_cast(float, r1);
 #endif
 }
 // keeps a wave-uniform two-way choice a BRANCH (the optimiser otherwise turns it into one v_cndmask per element)
@@ -191,14 +205,14 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float4 a = *reinterpret_cast<const float4*>(in.nrm + (long long)n * in.nrm_n_stride + 4LL * (4 * wave + i));
-            nra[i] = a.x * p_; nrb[i] = a.y * p_; nrs[i] = a.z;
+            nra[i] = hw_uniform(a.x * p_); nrb[i] = a.y * p_; nrs[i] = a.z;
         }
     }
     // the activation t > 0 ? t : t s in ONE branch-free instruction: for s <= 1 it is max(t, t s), for s > 1 min(t, t s) -- the median of (t, t s, +inf | -inf).  (A NaN
     // input never gets here as a result: its record's bound is non-finite and the whole sample is poisoned.)
     f32x4 nrk;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) nrk[i] = nrs[i] <= 1.0f ? __builtin_inff() : -__builtin_inff();
+    for (int i = 0; i < 4; ++i) nrk[i] = hw_uniform(nrs[i] <= 1.0f ? __builtin_inff() : -__builtin_inff());      // wave-uniform, but chosen by a vector compare: back into a scalar register
     // ---- staging loads: ONE buffer descriptor over the wave's four channel volumes; the plane advance lives in the lanes' byte offsets (two additions per
     // plane), the channel in the instruction's scalar offset (three constants) -- no descriptor arithmetic in the march ---------------------------------------
     const auto xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in.data + (long long)n * in.n_stride + (long long)(4 * wave) * DHW), 0, 0x7fffffff, 0x00020000);
@@ -213,15 +227,17 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
         xin[2] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(xrs, voff, cso2, 0)); \
         xin[3] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(xrs, voff, cso3, 0)); \
     }
+// packed over the PAIR (the two positions of a channel are the register pair a load returns: no register moves in front of the packed instructions); the activation,
+// one instruction per element anyway, writes the element of the 16-byte cell it belongs to
 #define MH_HW_CONV(DBO)                                                                               \
     {                                                                                                 \
         char* const db_ = ds + (DBO) + 16 * wave;                                                     \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                               \
-            f32x4 y_;                                                                                 \
-            const f32x4 t_ = __builtin_elementwise_fma(f32x4{xin[0][j], xin[1][j], xin[2][j], xin[3][j]}, nra, nrb), u_ = t_ * nrs; \
-            _Pragma("unroll") for (int i = 0; i < 4; ++i) y_[i] = __builtin_amdgcn_fmed3f(t_[i], u_[i], nrk[i]);      /* slope <= 1: max(t, t s), slope > 1: min(t, t s)  ==  t > 0 ? t : t s */ \
-            *reinterpret_cast<f32x4*>(db_ + loff[j]) = y_;                                            \
+        f32x4 y_[2];                                                                                  \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                               \
+            const f32x2 t_ = __builtin_elementwise_fma(xin[i], f32x2{nra[i], nra[i]}, f32x2{nrb[i], nrb[i]}), u_ = t_ * nrs[i]; \
+            _Pragma("unroll") for (int j = 0; j < 2; ++j) y_[j][i] = __builtin_amdgcn_fmed3f(t_[j], u_[j], nrk[i]);      /* slope <= 1: max(t, t s), slope > 1: min(t, t s)  ==  t > 0 ? t : t s */ \
         }                                                                                             \
+        _Pragma("unroll") for (int j = 0; j < 2; ++j) *reinterpret_cast<f32x4*>(db_ + loff[j]) = y_[j]; \
     }
     int staged = p_first;             // plane whose loads are in the registers
 #define MH_HW_ADV { voff += staged < p_last ? hw4 : 0u; staged += 1; }
@@ -284,8 +300,8 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
     {
         const int t_ = -((int)((__float_as_uint(wtail[1]) >> 23) & 0xffu) - 127) - e_in;      // wtail[1] = the weights' power-of-two scale
         const int t1_ = t_ / 2, t2_ = t_ - t1_;
-        inv_a = poisoned ? __uint_as_float(0x7fc00000u) : __uint_as_float((unsigned)(t1_ + 127) << 23);
-        inv_b = __uint_as_float((unsigned)(t2_ + 127) << 23);
+        inv_a = hw_uniform(poisoned ? __uint_as_float(0x7fc00000u) : __uint_as_float((unsigned)(t1_ + 127) << 23));
+        inv_b = hw_uniform(__uint_as_float((unsigned)(t2_ + 127) << 23));
     }
     const auto orsrc = __builtin_amdgcn_make_buffer_rsrc(out.data + (long long)n * out.n_stride + (long long)(cg * HWG_CN) * DHW, 0, (int)(HWG_CN * DHW * 4), 0x00020000);
     const unsigned ooff = 4u * (unsigned)((long long)co_l * DHW + (long long)(y0 + 2 * fty + fa) * W + x0 + 2 * ftx);
@@ -293,9 +309,15 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
     bool have_c = false;
     f32x4 s1 = {0.0f, 0.0f, 0.0f, 0.0f}, s2 = s1;
     const long long PHW = (long long)(H / 2) * (W / 2), PDHW = (long long)(D / 2) * PHW;
-    // POOL: lanes 0-31 store the maxima, lanes 32-63 the minima of their tile pair
-    const auto prs = __builtin_amdgcn_make_buffer_rsrc(POOL ? (fa ? pmin : pmax) + (long long)n * pool_n_stride + (long long)(cg * HWG_CN) * PDHW : out.data, 0, POOL ? (int)(HWG_CN * PDHW * 4) : 0, 0x00020000);
-    const unsigned poff = 4u * (unsigned)((long long)co_l * PDHW + (long long)((y0 >> 1) + fty) * (W / 2) + (x0 >> 1) + ftx);
+    // POOL: lanes 0-31 store the maxima, lanes 32-63 the minima of their tile pair.  Both buffers get a WAVE-UNIFORM descriptor (a descriptor chosen per lane is
+    // a loop over the distinct descriptors around every store) and every pooled plane two stores: the lanes that do not own the buffer carry bit 31 in their offset
+    // -- beyond every buffer, the hardware drops them; the store to the minima flips that bit.  The pooled plane is the instruction's scalar offset, and a plane
+    // that stores nothing (even, or not of this chunk) is a descriptor of zero bytes: a scalar choice of one descriptor word.
+    float* const pbase_mx = POOL ? pmax + (long long)n * pool_n_stride + (long long)(cg * HWG_CN) * PDHW : out.data;
+    float* const pbase_mn = POOL ? pmin + (long long)n * pool_n_stride + (long long)(cg * HWG_CN) * PDHW : out.data;
+    const int pbytes = POOL ? (int)(HWG_CN * PDHW * 4) : 0;
+    const unsigned phw4 = (unsigned)(PHW * 4);
+    const unsigned poff = (4u * (unsigned)((long long)co_l * PDHW + (long long)((y0 >> 1) + fty) * (W / 2) + (x0 >> 1) + ftx)) | (fa ? HWG_DROP : 0u);
     const float pk_ = fa ? -__builtin_inff() : __builtin_inff();
     f32x2 hm = {0.0f, 0.0f};                                 // POOL: the even plane's in-plane maxima (lanes 0-31) / minima (lanes 32-63)
     f32x4 pv = {0.0f, 0.0f, 0.0f, 0.0f};                     // ACC: the old values of the row being finished
@@ -345,10 +367,12 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
         }                                                                                             \
     }
     // output plane Q (ON: it exists and belongs to this chunk -- otherwise the stores go beyond the buffer and the statistics get weight 0):
-    // row a' = 0: Z_0 + Z_1 + Z_2, a' = 1: Z_1 - Z_2 - Z_3 with Z_i = the two column halves' sum; scale back, bias, (old values,) store, statistics, pooling
-#define MH_HW_FINISH(Q, ON)                                                                           \
+    // row a' = 0: Z_0 + Z_1 + Z_2, a' = 1: Z_1 - Z_2 - Z_3 with Z_i = the two column halves' sum; scale back, bias, (old values,) store, statistics, pooling.
+    // ST (a steady block, see the march): the plane is known to be ON and the pivot to be set -- the plane's byte offset is the store's scalar operand, the statistics
+    // lose their weight (d * 1 is d: the same bits) and nothing is chosen per plane but the pooled stores' parity
+#define MH_HW_FINISH(Q, ON, ST)                                                                       \
     {                                                                                                 \
-        const bool on_ = (ON);                                                                        \
+        const bool on_ = (ST) ? true : (ON);                                                          \
         const char* const zb_ = zs_ + ((Q) & 1) * HWG_ZB + zrd;                                       \
         f32x2 z0_[3], z1_[3];                                                                         \
         _Pragma("unroll") for (int i = 0; i < 3; ++i) {                                               \
@@ -360,22 +384,28 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
         const f32x2 y1_ = __builtin_elementwise_fma(z1_[2], fs_, __builtin_elementwise_fma(z1_[1], fs_, z1_[0])) * inv_a; \
         f32x4 o_ = {__builtin_fmaf(y0_[0], inv_b, bco), __builtin_fmaf(y1_[0], inv_b, bco), __builtin_fmaf(y0_[1], inv_b, bco), __builtin_fmaf(y1_[1], inv_b, bco)}; \
         if (ACC) o_ += pv;      /* the old values: requested at the start of this iteration's vector phase (a barrier and the transform ago) */ \
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o_), orsrc, on_ ? ooff + (unsigned)(Q) * (unsigned)(HW * 4) : HWG_DROP, 0, 0); \
+        if (ST) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o_), orsrc, ooff, (unsigned)(Q) * hw4, 0); \
+        else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o_), orsrc, on_ ? ooff + (unsigned)(Q) * hw4 : HWG_DROP, 0, 0); \
         if (STATS) {        /* sums of the deviations from a pivot (the lane's first value) and of their squares, branch-free: a plane that does not exist has weight 0 */ \
-            pivot = (on_ && !have_c) ? o_[0] : pivot;                                                 \
-            have_c = have_c || on_;                                                                   \
-            const f32x4 d_ = o_ - pivot, dw_ = d_ * (on_ ? 1.0f : 0.0f);                              \
+            if (!(ST)) {                                                                              \
+                pivot = (on_ && !have_c) ? o_[0] : pivot;                                             \
+                have_c = have_c || on_;                                                               \
+            }                                                                                         \
+            const f32x4 d_ = o_ - pivot, dw_ = (ST) ? d_ : d_ * (on_ ? 1.0f : 0.0f);                  \
             s1 += dw_;                                                                                \
             s2 = __builtin_elementwise_fma(dw_, d_, s2);                                              \
         }                                                                                             \
-        if (POOL && !(HWX_OFF & 32)) {         /* the tile pair's x pairs in-lane; the other row sits in lane ^ 32: lanes 0-31 (maxima) receive the partner's maxima, lanes 32-63 (minima) its minima */ \
+        if (POOL && !(HWX_OFF & 32)) {         /* the tile pair's x pairs in-lane; the other row sits in lane ^ 32: lanes 0-31 (maxima) end up with both rows' maxima, lanes 32-63 (minima) with both rows' minima */ \
             const f32x2 mx_ = {fmaxf(o_[0], o_[1]), fmaxf(o_[2], o_[3])}, mn_ = {fminf(o_[0], o_[1]), fminf(o_[2], o_[3])}; \
-            const f32x2 own_ = fa ? mn_ : mx_, snd_ = fa ? mx_ : mn_;                                 \
-            const f32x2 rcv_ = {hw_xchg32(snd_[0], fa), hw_xchg32(snd_[1], fa)};                      \
-            const f32x2 y_ = {__builtin_amdgcn_fmed3f(own_[0], rcv_[0], pk_), __builtin_amdgcn_fmed3f(own_[1], rcv_[1], pk_)};      /* pk_ = +inf: max, -inf: min */ \
+            float own0_, rcv0_, own1_, rcv1_;                                                         \
+            hw_xchg32_pair(mx_[0], mn_[0], fa, own0_, rcv0_);                                         \
+            hw_xchg32_pair(mx_[1], mn_[1], fa, own1_, rcv1_);                                         \
+            const f32x2 y_ = {__builtin_amdgcn_fmed3f(own0_, rcv0_, pk_), __builtin_amdgcn_fmed3f(own1_, rcv1_, pk_)};      /* pk_ = +inf: max, -inf: min */ \
             const f32x2 f_ = {__builtin_amdgcn_fmed3f(y_[0], hm[0], pk_), __builtin_amdgcn_fmed3f(y_[1], hm[1], pk_)}; \
-            const unsigned po_ = (on_ && ((Q) & 1) && !(HWX_OFF & 64)) ? poff + (unsigned)((Q) >> 1) * (unsigned)(PHW * 4) : HWG_DROP; \
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, f_), prs, po_, 0, 0);     \
+            const int pn_ = (on_ && ((Q) & 1) && !(HWX_OFF & 64)) ? pbytes : 0;                       \
+            const unsigned ps_ = (unsigned)((Q) >> 1) * phw4;                                         \
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, f_), __builtin_amdgcn_make_buffer_rsrc(pbase_mx, 0, pn_, 0x00020000), poff, ps_, 0); \
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, f_), __builtin_amdgcn_make_buffer_rsrc(pbase_mn, 0, pn_, 0x00020000), poff ^ HWG_DROP, ps_, 0); \
             hm = on_ ? y_ : hm;                                                                       \
         }                                                                                             \
     }
@@ -410,14 +440,19 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
     // multiplies in 2 P + 1, jp 1 in 2 P + 1 and 2 P + 2.  Plane P + 2 is staged in phases 2 P + 1 / 2 P + 2 into the buffer plane P - 1 was last read from in
     // phase 2 P - 1, and first read in phase 2 P + 4.  The Z halves of output plane q are written in phases 2 q + 3 / 2 q + 4, read in 2 q + 5 / 2 q + 6 (iteration
     // q + 2 of either pair) and their buffer (q & 1) is rewritten by plane q + 2 from phase 2 q + 7 on.
-#define MH_HW_ITER(P, R)                                                                              \
+    // ST = an iteration of a STEADY block (see the march below): the plane P exists, output plane P - 2 is finished and stored, output plane P - 1 leaves its Z halves
+    // -- known when the block is entered, so nothing of it is tested, chosen or masked per plane; the generic form tests every one of them on every plane
+#define MH_HW_ITER(P, R, ST)                                                                          \
     {                                                                                                 \
         constexpr int S0 = (3 - (R)) % 3, S1 = (S0 + 1) % 3, S2 = (S0 + 2) % 3;      /* R 0: (0, 1, 2), 1: (2, 0, 1), 2: (1, 2, 0) */ \
         constexpr int db0 = (R) * HWG_DB, db2 = (((R) + 2) % 3) * HWG_DB;            /* the iteration's own buffer and the one being staged: compile-time LDS offsets */ \
         const int p_ = (P);                                                                           \
-        const bool valid_ = p_ >= p_first && p_ <= p_last;                                            \
+        const bool valid_ = (ST) ? true : (p_ >= p_first && p_ <= p_last);                            \
         const int qf_ = p_ - 2;                                                                       \
-        if (ACC) { const bool nx_ = qf_ >= zs && qf_ < ze; pv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(orsrc, nx_ ? ooff + (unsigned)qf_ * hw4 : HWG_DROP, 0, 0)); } \
+        if (ACC) {                                                                                    \
+            if (ST) pv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(orsrc, ooff, (unsigned)qf_ * hw4, 0)); \
+            else { const bool nx_ = qf_ >= zs && qf_ < ze; pv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(orsrc, nx_ ? ooff + (unsigned)qf_ * hw4 : HWG_DROP, 0, 0)); } \
+        }                                                                                             \
         if (valid_) { if (!(HWX_OFF & 1)) MH_HW_XFORM(db0) }                                          \
         MH_HW_T(0)                                                                                    \
         __syncthreads();                                                                              \
@@ -425,15 +460,15 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
         if (valid_) {                                                                                 \
             __builtin_amdgcn_sched_barrier(0);                                                        \
             if (!(HWX_OFF & 2)) { MH_HW_CONV(db2) MH_HW_LDX MH_HW_ADV }                               \
-            if (!(HWX_OFF & 4)) MH_HW_FINISH(qf_, qf_ >= zs && qf_ < ze)                              \
+            if (!(HWX_OFF & 4)) MH_HW_FINISH(qf_, qf_ >= zs && qf_ < ze, ST)                          \
             if (!(HWX_OFF & 8)) MH_HW_MMS(S0, S1, S2)                                                 \
             MH_HW_DEAL                                                                                \
             __builtin_amdgcn_sched_barrier(0);                                                        \
         } else {                                                                                      \
             MH_HW_SKIP(S0)                                                                            \
-            if (!(HWX_OFF & 4)) MH_HW_FINISH(qf_, qf_ >= zs && qf_ < ze)                              \
+            if (!(HWX_OFF & 4)) MH_HW_FINISH(qf_, qf_ >= zs && qf_ < ze, false)                       \
         }                                                                                             \
-        if (!(HWX_OFF & 16)) if (p_ - 1 >= zs && p_ - 1 < ze) MH_HW_ZOUT(S2, p_ - 1)                  \
+        if (!(HWX_OFF & 16)) if ((ST) || (p_ - 1 >= zs && p_ - 1 < ze)) MH_HW_ZOUT(S2, p_ - 1)        \
         MH_HW_T(2)                                                                                    \
         __syncthreads();                                                                              \
         MH_HW_T(3)                                                                                    \
@@ -453,11 +488,19 @@ conv3d_k3_h2w_kernel(Tensor in, const uint4* __restrict__ wp, const float* __res
     }
     if (jp) __syncthreads();
     // whole blocks of three iterations up to p = ze + 1 (the iterations behind it find nothing to do but keep the barrier count)
-    for (int p = zs - 1; p <= ze + 1; p += 3) {
-        MH_HW_ITER(p, 0)
-        MH_HW_ITER(p + 1, 1)
-        MH_HW_ITER(p + 2, 2)
-    }
+    // A block is STEADY when all of its three iterations have their plane (p + 2 <= p_last), finish an output plane of this chunk (p - 2 >= zs, p < ze) and leave the
+    // Z halves of one (p + 1 < ze), and when the statistics' pivot is set -- by the first plane finished, in the chunk's second block: from the third block on.  Nine
+    // iterations of a chunk are generic (two blocks at its head, one at its end; twelve where the chunk's length leaves a block with a missing plane in front of the
+    // last one); a chunk too short for a steady block runs generic blocks only.  Both kinds
+    // are whole blocks of three with two barriers per iteration, so the buffers and accumulator sets keep rotating by name and the jp = 1 waves stay one phase behind.
+    int p = zs - 1;
+#define MH_HW_STEADY(P) ((P) >= zs + 5 && (P) + 2 <= p_last && (P) + 1 < ze)
+#define MH_HW_BLOCK(ST) { MH_HW_ITER(p, 0, ST) MH_HW_ITER(p + 1, 1, ST) MH_HW_ITER(p + 2, 2, ST) }
+    for (; p <= ze + 1 && !MH_HW_STEADY(p); p += 3) MH_HW_BLOCK(false)      // head (or the whole of a short chunk)
+    for (; MH_HW_STEADY(p); p += 3) MH_HW_BLOCK(true)
+    for (; p <= ze + 1; p += 3) MH_HW_BLOCK(false)                          // tail
+#undef MH_HW_BLOCK
+#undef MH_HW_STEADY
     if (!jp) __syncthreads();
 #ifdef HWX_PROF
     if (blockIdx.x == 0 && lane == 0) { _Pragma("unroll") for (int k = 0; k < 8; ++k) reinterpret_cast<long long*>(pmax)[wave * 8 + k] = tacc[k]; }
