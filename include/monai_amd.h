@@ -485,6 +485,29 @@ int64_t mh_minmax_workspace_floats(int C, int64_t n);
 int mh_minmax_f32(const float* src, int C, int64_t n, float* workspace, float* table, void* stream);
 int mh_minmax_scale_f32(const float* src, float* dst, int C, int64_t n, const float* table, int rescale, float b_scale, float b_min,
                         int flat_has_mul, float flat_mul, void* stream);
+/* Exact order statistics and percentiles of C runs of n contiguous fp32 values (C = 1: whole image; C = channels: channel_wise), the selection
+ * behind percentile() (monai/transforms/utils_pytorch_numpy_unification.py:104-136: above 1,000,000 elements a device-to-host copy and
+ * np.percentile, below a full torch.quantile sort).  A three-pass radix select (11 + 11 + 10 key bits) serves all ranks of all runs with the same
+ * launches; integer histograms only, the same bits on every run; no host synchronisation.  -0.0 and +0.0 are one value (a selected zero is +0.0),
+ * +-inf are ordinary values, a run that holds a NaN yields NaN for every rank.  n < 2^31 (MH_ERR_UNSUPPORTED beyond); every rank in [0, n).
+ * workspace: DEVICE, 16-byte aligned, mh_select_workspace_bytes(C) bytes, caller-owned.
+ * mh_order_statistics_f32: out (DEVICE float[C][R]) = the ranks[r]-th smallest value (0-based) of each run; ranks: HOST int64[R], R <= 4.
+ * mh_percentiles_f32: P <= 2 percentiles per run; ranks: HOST int64[2 P] = {lower, upper} order statistic of each percentile, weights: HOST
+ * double[P]; table (DEVICE float[C][P]) = the interpolation of the two in the arithmetic the reference ends up in: lerp_mode 0, torch.quantile
+ * (fp32 weight, at::lerp with one fused multiply-add: w < 0.5 ? fma(w, b - a, a) : fma(w - 1, b - a, b)); lerp_mode 1, np.percentile on an fp32
+ * array (numpy's _lerp: b - a rounded to fp32, then fp64 a + d t, b - d (1 - t) where t >= 0.5, one rounding to fp32). */
+int64_t mh_select_workspace_bytes(int C);
+int mh_order_statistics_f32(const float* src, int C, int64_t n, int R, const int64_t* ranks, void* workspace, float* out, void* stream);
+int mh_percentiles_f32(const float* src, int C, int64_t n, int P, const int64_t* ranks, const double* weights, int lerp_mode, void* workspace, float* table,
+                       void* stream);
+/* ScaleIntensityRangePercentiles (monai/transforms/intensity/array.py:1299-1418 over ScaleIntensityRange, 958-1012) with a_min / a_max read from
+ * table (DEVICE float[C][2], mh_percentiles_f32): dst = (src - lo) / (hi - lo) [* b_scale + b_min when rescale] [clamps]; hi - lo is subtracted in
+ * fp32 on the device; a run with hi - lo == 0 takes the reference's branch without division, rescale or clip: src - lo [+ b_min when flat_add]. */
+int mh_scale_intensity_table_f32(const float* src, float* dst, int C, int64_t n, const float* table, int rescale, float b_scale, float b_min, int flat_add,
+                                 int clip_lo, float lo, int clip_hi, float hi, void* stream);
+/* ClipIntensityPercentiles' hard clip (monai/transforms/intensity/array.py:1120-1122): dst = min(max(src, table[c][0]), table[c][1]) per run; a NaN
+ * voxel passes like torch.clamp, a NaN bound makes the whole run NaN. */
+int mh_clamp_table_f32(const float* src, float* dst, int C, int64_t n, const float* table, void* stream);
 /* Orientation (monai/transforms/spatial/functional.py:187-229: torch.flip over the reversed axes, then permute):
  * src [C][in_size3] -> dst [C][out], out axis k = input axis perm3[k] (HOST int32[3], a permutation of 0..2), input axis a
  * read backwards when flip3[a] != 0 (HOST int32[3]).  Images with fewer spatial axes pass leading extents of 1. */

@@ -90,6 +90,11 @@ SIGNATURES = {
     "mh_minmax_workspace_floats": (_L, [_I, _L]),
     "mh_minmax_f32": (_I, [_P, _I, _L, _P, _P, _P]),
     "mh_minmax_scale_f32": (_I, [_P, _P, _I, _L, _P, _I, _F, _F, _I, _F, _P]),
+    "mh_select_workspace_bytes": (_L, [_I]),
+    "mh_order_statistics_f32": (_I, [_P, _I, _L, _I, C.POINTER(C.c_int64), _P, _P, _P]),
+    "mh_percentiles_f32": (_I, [_P, _I, _L, _I, C.POINTER(C.c_int64), C.POINTER(C.c_double), _I, _P, _P, _P]),
+    "mh_scale_intensity_table_f32": (_I, [_P, _P, _I, _L, _P, _I, _F, _F, _I, _I, _F, _I, _F, _P]),
+    "mh_clamp_table_f32": (_I, [_P, _P, _I, _L, _P, _P]),
     "mh_nrm_identity_f32": (_I, [_P, _I, _I, _L, _P]),
     "mh_maxpool2_f32": (_I, [_T, _T, _P]),
     "mh_deconv_k2s2_f32": (_I, [_T, _P, _P, _T, _P]),

@@ -27,6 +27,7 @@
 #include "kernels/edt.h"
 #include "kernels/ccl.h"
 #include "kernels/preproc.h"
+#include "kernels/select.h"
 #include "kernels/nn_simple.h"
 #include "kernels/conv1x1_h2.h"
 #include "kernels/resample.h"
@@ -1650,6 +1651,96 @@ int mh_minmax_scale_f32(const float* src, float* dst, int C, int64_t n, const fl
     else
         hipLaunchKernelGGL(minmax_scale_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table, p);
     return launched("minmax_scale");
+}
+
+// ------------------------------------------------------------------------------------------ order statistics / percentiles (select.h)
+static inline int select_parts(int64_t n) {
+    const long long want = (n + 16383) / 16384;       // >= 64 values per lane
+    return (int)(want < 1 ? 1 : want > 1024 ? 1024 : want);
+}
+static inline size_t select_hist_words(int C) { return (size_t)3 * C * SEL_MAX_RANKS * SEL_BINS; }
+
+int64_t mh_select_workspace_bytes(int C) {
+    if (C < 1 || C > 65535) return fail(MH_ERR_ARG, "select: bad argument");
+    return (int64_t)(select_hist_words(C) * 4 + (size_t)C * sizeof(SelState) + (size_t)C * SEL_MAX_RANKS * 4);
+}
+
+static int select_checks(const char* what, const float* src, int C, int64_t n, int R, const int64_t* ranks, const void* workspace, const void* out) {
+    if (!src || !ranks || !workspace || !out || C < 1 || C > 65535 || n < 1 || R < 1 || R > SEL_MAX_RANKS) return fail(MH_ERR_ARG, "%s: bad argument", what);
+    if (!aligned(workspace, 16)) return fail(MH_ERR_ARG, "%s: workspace not 16-byte aligned", what);
+    if (n >= 2147483648LL) return fail(MH_ERR_UNSUPPORTED, "%s: runs of 2^31 or more values are not supported (n = %lld)", what, (long long)n);
+    for (int r = 0; r < R; ++r)
+        if (ranks[r] < 0 || ranks[r] >= n) return fail(MH_ERR_ARG, "%s: rank %lld outside [0, %lld)", what, (long long)ranks[r], (long long)n);
+    return MH_OK;
+}
+
+// the three counting passes and their scans; leaves float[C][R] at `os` (device).  Arguments checked by the caller.
+static int select_launch(const char* what, const float* src, int C, int64_t n, int R, const int64_t* ranks, void* workspace, float* os, hipStream_t s) {
+    unsigned* hist = static_cast<unsigned*>(workspace);
+    SelState* state = reinterpret_cast<SelState*>(hist + select_hist_words(C));
+    if (hipMemsetAsync(workspace, 0, select_hist_words(C) * 4 + (size_t)C * sizeof(SelState), s) != hipSuccess) return fail(MH_ERR_LAUNCH, "%s: memset failed", what);
+    SelRanks rk;
+    rk.R = R;
+    for (int r = 0; r < SEL_MAX_RANKS; ++r) rk.k[r] = r < R ? (unsigned)ranks[r] : 0u;
+    const bool vec = aligned(src, 16) && (C == 1 || n % 4 == 0);
+    const dim3 grid((unsigned)select_parts(n), (unsigned)C);
+    const size_t per_pass = (size_t)C * SEL_MAX_RANKS * SEL_BINS;
+#define MH_SEL_PASS(P_)                                                                                                                                \
+    if (vec) hipLaunchKernelGGL((select_count_kernel<P_, true>), grid, dim3(256), 0, s, src, (long long)n, hist + (P_) * per_pass, state);            \
+    else hipLaunchKernelGGL((select_count_kernel<P_, false>), grid, dim3(256), 0, s, src, (long long)n, hist + (P_) * per_pass, state);               \
+    hipLaunchKernelGGL(select_scan_kernel<P_>, dim3((unsigned)C), dim3(256), 0, s, (const unsigned*)(hist + (P_) * per_pass), state, rk, os)
+    MH_SEL_PASS(0);
+    MH_SEL_PASS(1);
+    MH_SEL_PASS(2);
+#undef MH_SEL_PASS
+    return MH_OK;
+}
+
+int mh_order_statistics_f32(const float* src, int C, int64_t n, int R, const int64_t* ranks, void* workspace, float* out, void* stream) {
+    if (int rc = select_checks("order_statistics", src, C, n, R, ranks, workspace, out)) return rc;
+    if (int rc = select_launch("order_statistics", src, C, n, R, ranks, workspace, out, (hipStream_t)stream)) return rc;
+    return launched("order_statistics");
+}
+
+int mh_percentiles_f32(const float* src, int C, int64_t n, int P, const int64_t* ranks, const double* weights, int lerp_mode, void* workspace, float* table,
+                       void* stream) {
+    if (P < 1 || P > SEL_MAX_RANKS / 2 || !weights || (lerp_mode != SEL_LERP_TORCH && lerp_mode != SEL_LERP_NUMPY)) return fail(MH_ERR_ARG, "percentiles: bad argument");
+    if (int rc = select_checks("percentiles", src, C, n, 2 * P, ranks, workspace, table)) return rc;
+    for (int p = 0; p < P; ++p)
+        if (!(weights[p] >= 0.0)) return fail(MH_ERR_ARG, "percentiles: negative or NaN weight");
+    float* os = reinterpret_cast<float*>(static_cast<char*>(workspace) + select_hist_words(C) * 4 + (size_t)C * sizeof(SelState));
+    if (int rc = select_launch("percentiles", src, C, n, 2 * P, ranks, workspace, os, (hipStream_t)stream)) return rc;
+    SelLerp lp;
+    lp.P = P; lp.mode = lerp_mode;
+    for (int p = 0; p < SEL_MAX_RANKS / 2; ++p) lp.w[p] = p < P ? weights[p] : 0.0;
+    hipLaunchKernelGGL(percentile_lerp_kernel, dim3((unsigned)((C * P + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (const float*)os, C, lp, table);
+    return launched("percentiles");
+}
+
+int mh_scale_intensity_table_f32(const float* src, float* dst, int C, int64_t n, const float* table, int rescale, float b_scale, float b_min, int flat_add,
+                                 int clip_lo, float lo, int clip_hi, float hi, void* stream) {
+    if (!src || !dst || !table || C < 1 || C > 65535 || n < 1) return fail(MH_ERR_ARG, "scale_intensity_table: bad argument");
+    if (n > 0x7fffffffLL * 1024) return fail(MH_ERR_UNSUPPORTED, "scale_intensity_table: problem too large for one launch");
+    TableScale p;
+    p.b_scale = b_scale; p.b_min = b_min; p.lo = lo; p.hi = hi;
+    p.rescale = rescale != 0; p.flat_add = flat_add != 0; p.clip_lo = clip_lo != 0; p.clip_hi = clip_hi != 0;
+    const dim3 grid(blocks_for((n + 3) / 4), (unsigned)C);
+    if (aligned(src, 16) && aligned(dst, 16) && n % 4 == 0)
+        hipLaunchKernelGGL(table_scale_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table, p);
+    else
+        hipLaunchKernelGGL(table_scale_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table, p);
+    return launched("scale_intensity_table");
+}
+
+int mh_clamp_table_f32(const float* src, float* dst, int C, int64_t n, const float* table, void* stream) {
+    if (!src || !dst || !table || C < 1 || C > 65535 || n < 1) return fail(MH_ERR_ARG, "clamp_table: bad argument");
+    if (n > 0x7fffffffLL * 1024) return fail(MH_ERR_UNSUPPORTED, "clamp_table: problem too large for one launch");
+    const dim3 grid(blocks_for((n + 3) / 4), (unsigned)C);
+    if (aligned(src, 16) && aligned(dst, 16) && n % 4 == 0)
+        hipLaunchKernelGGL(table_clamp_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table);
+    else
+        hipLaunchKernelGGL(table_clamp_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table);
+    return launched("clamp_table");
 }
 
 int mh_flip_permute_f32(const float* src, float* dst, int C, const int32_t* in_size3, const int32_t* perm3, const int32_t* flip3, void* stream) {

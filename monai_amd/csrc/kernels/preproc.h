@@ -291,4 +291,69 @@ __global__ void __launch_bounds__(256) minmax_scale_kernel(const float* __restri
     for (long long j = i; j < n && j < i + 4; ++j) dst[off + j] = minmax_scale_one(src[off + j], mn, div, flat, p);
 }
 
+// ScaleIntensityRangePercentiles (monai/transforms/intensity/array.py:1299-1418): ScaleIntensityRange (958-1012) with a_min / a_max read from a device
+// table {lo, hi} per run (select.h).  hi - lo is formed here in fp32 (the reference subtracts two fp32 0-d tensors); a run with hi - lo == 0 takes the
+// reference's branch without a division, a clip or a rescale: x - lo, plus b_min when one is given.  Otherwise scale_range_one's roundings.
+struct TableScale {
+    float b_scale, b_min, lo, hi;
+    int rescale, flat_add, clip_lo, clip_hi;
+};
+__device__ __forceinline__ float table_scale_one(float x, float a_min, float div, bool flat, const TableScale& p) {
+    if (flat) {
+        float v = x - a_min;
+        if (p.flat_add) v = v + p.b_min;
+        return v;
+    }
+    float v = (x - a_min) / div;
+    if (p.rescale) { v = v * p.b_scale; v = v + p.b_min; }
+    if (p.clip_lo && v < p.lo) v = p.lo;
+    if (p.clip_hi && v > p.hi) v = p.hi;
+    return v;
+}
+template <bool VEC>
+__global__ void __launch_bounds__(256) table_scale_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n,
+                                                          const float* __restrict__ table, TableScale p) {
+    const long long off = (long long)blockIdx.y * n;
+    const float a_min = table[2 * blockIdx.y], a_max = table[2 * blockIdx.y + 1];
+    const float div = a_max - a_min;
+    const bool flat = div == 0.0f;
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    if (VEC && i + 4 <= n) {
+        const float4 v = *reinterpret_cast<const float4*>(src + off + i);
+        float4 r;
+        r.x = table_scale_one(v.x, a_min, div, flat, p); r.y = table_scale_one(v.y, a_min, div, flat, p);
+        r.z = table_scale_one(v.z, a_min, div, flat, p); r.w = table_scale_one(v.w, a_min, div, flat, p);
+        *reinterpret_cast<float4*>(dst + off + i) = r;
+        return;
+    }
+    for (long long j = i; j < n && j < i + 4; ++j) dst[off + j] = table_scale_one(src[off + j], a_min, div, flat, p);
+}
+
+// ClipIntensityPercentiles' hard clip (array.py:1120-1122): torch.clamp(x, lo, hi) with tensor bounds per run: min(max(x, lo), hi); a NaN voxel passes,
+// a NaN bound makes the run NaN.
+__device__ __forceinline__ float table_clamp_one(float x, float lo, float hi, bool bad) {
+    if (bad) return NAN;
+    if (x < lo) x = lo;
+    if (x > hi) x = hi;
+    return x;
+}
+template <bool VEC>
+__global__ void __launch_bounds__(256) table_clamp_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n, const float* __restrict__ table) {
+    const long long off = (long long)blockIdx.y * n;
+    const float lo = table[2 * blockIdx.y], hi = table[2 * blockIdx.y + 1];
+    const bool bad = lo != lo || hi != hi;
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    if (VEC && i + 4 <= n) {
+        const float4 v = *reinterpret_cast<const float4*>(src + off + i);
+        float4 r;
+        r.x = table_clamp_one(v.x, lo, hi, bad); r.y = table_clamp_one(v.y, lo, hi, bad);
+        r.z = table_clamp_one(v.z, lo, hi, bad); r.w = table_clamp_one(v.w, lo, hi, bad);
+        *reinterpret_cast<float4*>(dst + off + i) = r;
+        return;
+    }
+    for (long long j = i; j < n && j < i + 4; ++j) dst[off + j] = table_clamp_one(src[off + j], lo, hi, bad);
+}
+
 }  // namespace mh

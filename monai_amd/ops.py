@@ -1033,6 +1033,96 @@ def minmax_scale(src: torch.Tensor, channels: int, n: int, b_scale: Optional[flo
     return out
 
 
+PERCENTILE_NUMPY_ABOVE = 1_000_000      # percentile() hands tensors of MORE elements than this to np.percentile (utils_pytorch_numpy_unification.py:129)
+
+
+def _select_args(src: torch.Tensor, channels: int, n: int, what: str):
+    _lib.require_device(src)
+    if channels < 1 or n < 1 or not src.is_contiguous() or src.numel() != channels * n:
+        raise RuntimeError(f"monai_amd.{what}: contiguous tensor of channels * n elements required (channels, n >= 1)")
+    L = _lib.lib()
+    ws = torch.empty(L.query("mh_select_workspace_bytes", int(channels)) // 4, dtype=torch.int32, device=src.device)
+    return L, ws
+
+
+def order_statistics(src: torch.Tensor, channels: int, n: int, ranks: Sequence[int]) -> torch.Tensor:
+    """The ``ranks[r]``-th smallest value (0-based) of each of the ``channels`` runs of ``n`` contiguous float32 values of ``src``: a device
+    table ``[channels, len(ranks)]`` (at most 4 ranks), exact and the same bits on every run.  ``-0.0`` and ``+0.0`` are one value (a selected
+    zero is ``+0.0``); a run that holds a NaN gives NaN for every rank.  No host synchronisation."""
+    L, ws = _select_args(src, channels, n, "order_statistics")
+    ranks = [int(k) for k in ranks]
+    out = torch.empty((int(channels), len(ranks)), dtype=torch.float32, device=src.device)
+    L.call("mh_order_statistics_f32", _lib.ptr(src), int(channels), int(n), len(ranks), (C.c_int64 * len(ranks))(*ranks), _lib.ptr(ws), _lib.ptr(out), _s(src))
+    return out
+
+
+def percentile_ranks(n: int, q: float, numpy_rule: bool):
+    """(lower rank, upper rank, weight) of the ``q``-th percentile (0 .. 100) of ``n`` values, as the reference's ``percentile()`` ends up computing them.
+    numpy_rule: np.percentile, method "linear" -- ``q / float32(100)`` and the virtual index ``(n - 1) q`` in fp64, neighbours ``floor`` and
+    ``floor + 1`` (both ``n - 1`` at the upper end).  Otherwise torch.quantile -- ``q / 100`` rounded to fp32, the rank ``q (n - 1)`` in fp32,
+    neighbours ``floor`` and ``ceil``, an fp32 weight."""
+    import numpy as np
+
+    if numpy_rule:
+        vi = (n - 1) * np.true_divide(np.asarray(q), np.float32(100))
+        if vi >= n - 1:
+            return n - 1, n - 1, float(vi + 1)
+        lo = np.floor(vi)
+        return int(lo), int(lo) + 1, float(vi - lo)
+    rank = np.float32(np.float64(q) / 100.0) * np.float32(n - 1)
+    lo, hi = np.floor(rank), np.ceil(rank)
+    return int(lo), int(hi), float(np.float32(rank - lo))
+
+
+def percentiles(src: torch.Tensor, channels: int, n: int, qs: Sequence[float]) -> torch.Tensor:
+    """The percentiles ``qs`` (0 .. 100, at most two) of each of the ``channels`` runs of ``n`` contiguous float32 values of ``src`` as a device table
+    ``[channels, len(qs)]``: what the reference's ``percentile()`` (monai/transforms/utils_pytorch_numpy_unification.py:104-136) returns for each run,
+    from an exact radix select on the device -- three reads of the data for all runs and percentiles together, no sort, no copy to the host, no host
+    synchronisation.  The regime follows the reference per run: ``n > 1_000_000`` is np.percentile's arithmetic (fp64 virtual index and
+    interpolation, one rounding to fp32), otherwise torch.quantile's (fp32 rank and weight, ``at::lerp`` with its fused multiply-add)."""
+    L, ws = _select_args(src, channels, n, "percentiles")
+    qs = [float(q) for q in qs]
+    if any(not (0.0 <= q <= 100.0) for q in qs):
+        raise ValueError(f"q values must be in [0, 100], got values: {qs}.")
+    numpy_rule = n > PERCENTILE_NUMPY_ABOVE
+    ranks, weights = [], []
+    for q in qs:
+        lo, hi, w = percentile_ranks(int(n), q, numpy_rule)
+        ranks += [lo, hi]
+        weights.append(w)
+    table = torch.empty((int(channels), len(qs)), dtype=torch.float32, device=src.device)
+    L.call("mh_percentiles_f32", _lib.ptr(src), int(channels), int(n), len(qs), (C.c_int64 * len(ranks))(*ranks), (C.c_double * len(weights))(*weights),
+           int(numpy_rule), _lib.ptr(ws), _lib.ptr(table), _s(src))
+    return table
+
+
+def _table_args(src: torch.Tensor, channels: int, n: int, table: torch.Tensor, what: str) -> None:
+    _lib.require_device(src, table)
+    if channels < 1 or n < 1 or not src.is_contiguous() or src.numel() != channels * n or not table.is_contiguous() or tuple(table.shape) != (channels, 2):
+        raise RuntimeError(f"monai_amd.{what}: contiguous tensor of channels * n elements and a contiguous [channels, 2] table required")
+
+
+def scale_intensity_table(src: torch.Tensor, channels: int, n: int, table: torch.Tensor, b_scale: Optional[float], b_min: Optional[float],
+                          lo: Optional[float], hi: Optional[float]) -> torch.Tensor:
+    """ScaleIntensityRange with ``a_min, a_max = table[c]`` read on the device, per run of n values: ``(x - a_min) / (a_max - a_min)``
+    [``* b_scale + b_min`` when b_scale is not None] [clamped to lo / hi where given]; a run with ``a_max - a_min == 0`` becomes ``x - a_min``
+    [``+ b_min`` when b_min is not None], the reference's branch without a division."""
+    _table_args(src, channels, n, table, "scale_intensity_table")
+    out = torch.empty_like(src)
+    _lib.lib().call("mh_scale_intensity_table_f32", _lib.ptr(src), _lib.ptr(out), int(channels), int(n), _lib.ptr(table), int(b_scale is not None),
+                    float(b_scale or 0.0), float(b_min or 0.0), int(b_min is not None), int(lo is not None), float(lo or 0.0), int(hi is not None),
+                    float(hi or 0.0), _s(src))
+    return out
+
+
+def clamp_table(src: torch.Tensor, channels: int, n: int, table: torch.Tensor) -> torch.Tensor:
+    """``torch.clamp(x, table[c][0], table[c][1])`` per run of n values, the bounds read on the device (a NaN voxel passes, a NaN bound gives NaN)."""
+    _table_args(src, channels, n, table, "clamp_table")
+    out = torch.empty_like(src)
+    _lib.lib().call("mh_clamp_table_f32", _lib.ptr(src), _lib.ptr(out), int(channels), int(n), _lib.ptr(table), _s(src))
+    return out
+
+
 _OV_DTYPES = {torch.float32: 0, torch.uint8: 1, torch.bool: 1, torch.int64: 2}
 
 

@@ -68,6 +68,7 @@ _TARGETS = {
         "ScaleIntensityRange": ("monai_amd.transforms.intensity.array", "ScaleIntensityRange"),
         "NormalizeIntensity": ("monai_amd.transforms.intensity.array", "NormalizeIntensity"),
         "ScaleIntensity": ("monai_amd.transforms.intensity.array", "ScaleIntensity"),
+        **{n: ("monai_amd.transforms.intensity.array", n) for n in ("ScaleIntensityRangePercentiles", "ClipIntensityPercentiles")},
     },
     "monai.transforms.croppad.array": {n: ("monai_amd.transforms.croppad.array", n) for n in
                                        ("CropForeground", "Pad", "SpatialPad", "BorderPad", "DivisiblePad", "Crop", "SpatialCrop", "CenterSpatialCrop")},
@@ -110,6 +111,8 @@ _TARGETS = {
         "ScaleIntensityd": ("monai_amd.transforms.intensity.dictionary", "ScaleIntensityd"),
         "ScaleIntensityD": ("monai_amd.transforms.intensity.dictionary", "ScaleIntensityd"),
         "ScaleIntensityDict": ("monai_amd.transforms.intensity.dictionary", "ScaleIntensityd"),
+        **{n + suffix: ("monai_amd.transforms.intensity.dictionary", n + "d") for n in ("ScaleIntensityRangePercentiles", "ClipIntensityPercentiles")
+           for suffix in ("d", "D", "Dict")},
     },
     "monai.networks.layers.spatial_transforms": {
         "AffineTransform": ("monai_amd.networks.layers.spatial_transforms", "AffineTransform"),

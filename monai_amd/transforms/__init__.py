@@ -8,6 +8,10 @@ from .intensity import (  # noqa: F401
     NormalizeIntensityd, ScaleIntensity, ScaleIntensityD, ScaleIntensityDict, ScaleIntensityd, ScaleIntensityRange, ScaleIntensityRangeD, ScaleIntensityRangeDict,
     ScaleIntensityRanged,
 )
+from .intensity import ClipIntensityPercentiles, ClipIntensityPercentilesD, ClipIntensityPercentilesDict, ClipIntensityPercentilesd  # noqa: F401
+from .intensity import (  # noqa: F401
+    ScaleIntensityRangePercentiles, ScaleIntensityRangePercentilesD, ScaleIntensityRangePercentilesDict, ScaleIntensityRangePercentilesd,
+)
 from .spatial import Flip, FlipD, FlipDict, Flipd, Rotate90, Rotate90D, Rotate90Dict, Rotate90d  # noqa: F401
 from .spatial import Orientation, OrientationD, OrientationDict, Orientationd, Resample, SpatialResample, Spacing, SpacingD, SpacingDict, Spacingd, spatial_resample  # noqa: F401
 from .post import Activations, ActivationsD, ActivationsDict, Activationsd, AsDiscrete, AsDiscreteD, AsDiscreteDict, AsDiscreted  # noqa: F401

@@ -1,5 +1,7 @@
-from .array import GaussianSmooth, NormalizeIntensity, ScaleIntensity, ScaleIntensityRange  # noqa: F401
+from .array import ClipIntensityPercentiles, GaussianSmooth, NormalizeIntensity, ScaleIntensity, ScaleIntensityRange, ScaleIntensityRangePercentiles  # noqa: F401
 from .dictionary import (  # noqa: F401
-    GaussianSmoothD, GaussianSmoothDict, GaussianSmoothd, NormalizeIntensityD, NormalizeIntensityDict, NormalizeIntensityd, ScaleIntensityD,
-    ScaleIntensityDict, ScaleIntensityRangeD, ScaleIntensityRangeDict, ScaleIntensityRanged, ScaleIntensityd,
+    ClipIntensityPercentilesD, ClipIntensityPercentilesDict, ClipIntensityPercentilesd, GaussianSmoothD, GaussianSmoothDict, GaussianSmoothd,
+    NormalizeIntensityD, NormalizeIntensityDict, NormalizeIntensityd, ScaleIntensityD, ScaleIntensityDict, ScaleIntensityRangeD,
+    ScaleIntensityRangeDict, ScaleIntensityRangePercentilesD, ScaleIntensityRangePercentilesDict, ScaleIntensityRangePercentilesd,
+    ScaleIntensityRanged, ScaleIntensityd,
 )

@@ -1,16 +1,19 @@
-"""``GaussianSmooth`` (monai/transforms/intensity/array.py:1590-1622, the fused smoothing kernel) and ``ScaleIntensityRange``
-(array.py:958-1012, one element-wise pass)."""
+"""``GaussianSmooth`` (monai/transforms/intensity/array.py:1590-1622, the fused smoothing kernel), ``ScaleIntensityRange``
+(array.py:958-1012, one element-wise pass), ``NormalizeIntensity``, ``ScaleIntensity`` and the percentile transforms
+``ScaleIntensityRangePercentiles`` (array.py:1299-1418) and ``ClipIntensityPercentiles`` (array.py:1015-1157) on the exact
+order-statistic kernel."""
 
 from __future__ import annotations
 
 from collections.abc import Sequence
 
+import numpy as np
 import torch
 
 from ...data.meta_tensor import is_meta
 from ...networks.layers.simplelayers import GaussianFilter
 
-__all__ = ["GaussianSmooth", "ScaleIntensityRange", "NormalizeIntensity", "ScaleIntensity"]
+__all__ = ["GaussianSmooth", "ScaleIntensityRange", "NormalizeIntensity", "ScaleIntensity", "ScaleIntensityRangePercentiles", "ClipIntensityPercentiles"]
 
 
 class GaussianSmooth:
@@ -175,3 +178,104 @@ class ScaleIntensity:
         if is_meta(img):
             return type(img)(out, meta=dict(img.meta), applied_operations=list(getattr(img, "applied_operations", [])))
         return out
+
+
+def _percentile_input(img, name: str, channel_wise: bool):
+    """the float32 image as a contiguous tensor, the number of runs and their length"""
+    data = img.as_tensor() if is_meta(img) else torch.as_tensor(img)
+    if data.dtype != torch.float32:
+        raise NotImplementedError(f"monai_amd.{name}: {data.dtype} images are not on the HIP path (float32 images are)")
+    x = data.contiguous()
+    c = int(x.shape[0]) if channel_wise and x.dim() > 0 else 1
+    if not x.numel() or c < 1:
+        raise NotImplementedError(f"monai_amd.{name}: an empty image has no percentiles")
+    return x, c, x.numel() // c
+
+
+class ScaleIntensityRangePercentiles:
+    """``monai.transforms.ScaleIntensityRangePercentiles`` (monai/transforms/intensity/array.py:1299-1418): ScaleIntensityRange from the image's
+    (or, ``channel_wise``, each channel's) own ``lower`` / ``upper`` intensity percentiles to ``[b_min, b_max]``; ``relative`` scales to the
+    corresponding percentiles of ``[b_min, b_max]`` instead (computed on the host in doubles, as the reference does).  The percentiles come from an
+    exact radix select on the device (csrc/kernels/select.h) and stay in device memory for the apply pass: the reference's copy of every image
+    above 1,000,000 elements to the host, its ``np.percentile`` there and its full sort below that size do not exist here, and nothing is
+    read back.  The percentile values reproduce the reference's two regimes (np.percentile above 1,000,000 elements per call, torch.quantile
+    below) and the apply pass keeps ScaleIntensityRange's fp32 operator sequence.
+
+    One deliberate difference: a constant image (``a_min == a_max``) takes the reference's branch without a division -- decided on the
+    device -- but the reference's ``"Divide by zero (a_min == a_max)"`` warning is NOT issued: it would need the values on the host.
+    float32 images only; other dtypes are not on the HIP path."""
+
+    def __init__(self, lower: float, upper: float, b_min: float | None, b_max: float | None, clip: bool = False, relative: bool = False,
+                 channel_wise: bool = False, dtype=np.float32) -> None:
+        if lower < 0.0 or lower > 100.0:
+            raise ValueError("Percentiles must be in the range [0, 100]")
+        if upper < 0.0 or upper > 100.0:
+            raise ValueError("Percentiles must be in the range [0, 100]")
+        self.lower, self.upper, self.b_min, self.b_max = lower, upper, b_min, b_max
+        self.clip, self.relative, self.channel_wise, self.dtype = clip, relative, channel_wise, dtype
+
+    def __call__(self, img):
+        from ... import ops
+
+        x, c, n = _percentile_input(img, "ScaleIntensityRangePercentiles", self.channel_wise)
+        dtype = _to_torch_dtype(self.dtype) or x.dtype
+        b_min, b_max = self.b_min, self.b_max
+        if self.relative:
+            if (self.b_min is None) or (self.b_max is None):
+                raise ValueError("If it is relative, b_min and b_max should not be None.")
+            b_min = ((self.b_max - self.b_min) * (self.lower / 100.0)) + self.b_min
+            b_max = ((self.b_max - self.b_min) * (self.upper / 100.0)) + self.b_min
+        if self.clip and b_min is None and b_max is None:       # array.py:1009 -> torch.clamp(img, None, None)
+            raise RuntimeError("torch.clamp: At least one of 'min' or 'max' must not be None")
+        table = ops.percentiles(x, c, n, (self.lower, self.upper))
+        rescale = b_min is not None and b_max is not None
+        out = ops.scale_intensity_table(x, c, n, table, (b_max - b_min) if rescale else None, b_min, b_min if self.clip else None,
+                                        b_max if self.clip else None)
+        if out.dtype != dtype:
+            out = out.to(dtype)
+        if is_meta(img):
+            return type(img)(out, meta=dict(img.meta), applied_operations=list(getattr(img, "applied_operations", [])))
+        return out
+
+
+class ClipIntensityPercentiles:
+    """``monai.transforms.ClipIntensityPercentiles`` (monai/transforms/intensity/array.py:1015-1157), the hard clip: ``torch.clamp`` of the image
+    (or, ``channel_wise``, of each channel) to its own ``lower`` / ``upper`` intensity percentiles; a ``None`` bound is percentile 0 / 100.  The
+    percentiles come from the exact radix select on the device (csrc/kernels/select.h) and are read by the clamp pass from device memory; only
+    ``return_clipping_values=True`` reads them back -- one device-to-host copy of the whole table -- to fill ``meta["clipping_values"]`` the way
+    the reference does (the list the instance keeps, one ``(lower, upper)`` tuple appended per image or per channel).  ``dtype`` only reaches the
+    reference's soft clip, as there.  The soft clip (``sharpness_factor``) and images other than float32 are not on the HIP path."""
+
+    def __init__(self, lower: float | None, upper: float | None, sharpness_factor: float | None = None, channel_wise: bool = False,
+                 return_clipping_values: bool = False, dtype=np.float32) -> None:
+        if lower is None and upper is None:
+            raise ValueError("lower or upper percentiles must be provided")
+        if lower is not None and (lower < 0.0 or lower > 100.0):
+            raise ValueError("Percentiles must be in the range [0, 100]")
+        if upper is not None and (upper < 0.0 or upper > 100.0):
+            raise ValueError("Percentiles must be in the range [0, 100]")
+        if upper is not None and lower is not None and upper < lower:
+            raise ValueError("upper must be greater than or equal to lower")
+        if sharpness_factor is not None and sharpness_factor <= 0:
+            raise ValueError("sharpness_factor must be greater than 0")
+        if sharpness_factor is not None:
+            raise NotImplementedError("monai_amd.ClipIntensityPercentiles: the soft clip (sharpness_factor) is not on the HIP path")
+        self.lower, self.upper, self.sharpness_factor, self.channel_wise = lower, upper, sharpness_factor, channel_wise
+        if return_clipping_values:
+            self.clipping_values: list = []
+        self.return_clipping_values, self.dtype = return_clipping_values, dtype
+
+    def __call__(self, img):
+        from ... import ops
+        from ...data.meta_tensor import MetaTensor
+
+        x, c, n = _percentile_input(img, "ClipIntensityPercentiles", self.channel_wise)
+        table = ops.percentiles(x, c, n, (0.0 if self.lower is None else self.lower, 100.0 if self.upper is None else self.upper))
+        out = ops.clamp_table(x, c, n, table)
+        meta = dict(img.meta) if is_meta(img) else {}
+        if self.return_clipping_values:
+            self.clipping_values.extend((float(lo), float(hi)) for lo, hi in table.cpu().tolist())      # the one device-to-host read
+            meta["clipping_values"] = self.clipping_values
+        if is_meta(img):
+            return type(img)(out, meta=meta, applied_operations=list(getattr(img, "applied_operations", [])))
+        return MetaTensor(out, meta=meta) if self.return_clipping_values else out

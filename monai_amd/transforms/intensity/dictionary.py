@@ -2,11 +2,15 @@
 
 from __future__ import annotations
 
+import numpy as np
+
 from ...utils.misc import ensure_tuple
-from .array import GaussianSmooth, NormalizeIntensity, ScaleIntensity, ScaleIntensityRange
+from .array import ClipIntensityPercentiles, GaussianSmooth, NormalizeIntensity, ScaleIntensity, ScaleIntensityRange, ScaleIntensityRangePercentiles
 
 __all__ = ["GaussianSmoothd", "GaussianSmoothD", "GaussianSmoothDict", "ScaleIntensityRanged", "ScaleIntensityRangeD", "ScaleIntensityRangeDict",
-           "NormalizeIntensityd", "NormalizeIntensityD", "NormalizeIntensityDict", "ScaleIntensityd", "ScaleIntensityD", "ScaleIntensityDict"]
+           "NormalizeIntensityd", "NormalizeIntensityD", "NormalizeIntensityDict", "ScaleIntensityd", "ScaleIntensityD", "ScaleIntensityDict",
+           "ScaleIntensityRangePercentilesd", "ScaleIntensityRangePercentilesD", "ScaleIntensityRangePercentilesDict",
+           "ClipIntensityPercentilesd", "ClipIntensityPercentilesD", "ClipIntensityPercentilesDict"]
 
 
 class GaussianSmoothd:
@@ -65,3 +69,28 @@ class ScaleIntensityd(GaussianSmoothd):
 
 
 ScaleIntensityD = ScaleIntensityDict = ScaleIntensityd
+
+
+class ScaleIntensityRangePercentilesd(GaussianSmoothd):
+    """Dictionary version of :class:`ScaleIntensityRangePercentiles` (monai/transforms/intensity/dictionary.py:895-948)."""
+
+    def __init__(self, keys, lower: float, upper: float, b_min, b_max, clip: bool = False, relative: bool = False, channel_wise: bool = False,
+                 dtype=np.float32, allow_missing_keys: bool = False) -> None:
+        self.keys = ensure_tuple(keys)
+        self.allow_missing_keys = allow_missing_keys
+        self.scaler = self.converter = ScaleIntensityRangePercentiles(lower, upper, b_min, b_max, clip, relative, channel_wise, dtype)
+
+
+ScaleIntensityRangePercentilesD = ScaleIntensityRangePercentilesDict = ScaleIntensityRangePercentilesd
+
+
+class ClipIntensityPercentilesd(GaussianSmoothd):
+    """Dictionary version of :class:`ClipIntensityPercentiles` (monai/transforms/intensity/dictionary.py:951-989)."""
+
+    def __init__(self, keys, lower, upper, sharpness_factor=None, channel_wise: bool = False, dtype=np.float32, allow_missing_keys: bool = False) -> None:
+        self.keys = ensure_tuple(keys)
+        self.allow_missing_keys = allow_missing_keys
+        self.scaler = self.converter = ClipIntensityPercentiles(lower=lower, upper=upper, sharpness_factor=sharpness_factor, channel_wise=channel_wise, dtype=dtype)
+
+
+ClipIntensityPercentilesD = ClipIntensityPercentilesDict = ClipIntensityPercentilesd
