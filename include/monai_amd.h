@@ -632,6 +632,21 @@ int mh_cc_filter(const void* src, void* dst, int dtype, int64_t n, const double*
 int mh_separable_filter3d_f32(const float* src, float* dst, int NC, int D, int H, int W, const float* kz, int kz_n,
                               const float* ky, int ky_n, const float* kx, int kx_n, void* stream);
 
+/* ---- Median filtering (MedianSmooth / MedianFilter / median_filter) ------------------------------------------ */
+
+/* dst = the median of src over a box window of radii (rz, ry, rx) with replicate padding (indices clamped to the volume), per image
+ * [n][D][H][W] -- median_filter / MedianFilter.forward (monai/networks/layers/simplelayers.py:441-539: replicate F.pad, a one-hot
+ * convolution that writes every voxel's window as (2 rz + 1)(2 ry + 1)(2 rx + 1) channels, torch.median over them) and MedianSmooth
+ * (monai/transforms/intensity/array.py) over it.  2-D images pass D = 1 and rz = 0, 1-D images D = H = 1 and rz = ry = 0.  An exact
+ * selection: finite inputs give the reference's bits; a selected -0.0 is written as +0.0 and a window that holds +-inf or NaN gives NaN,
+ * as the reference's multiplications by the one-hot zeros do.  No atomics, the same bits on every run; no workspace.  src != dst.
+ * Windows of more than 343 values (7^3), more than 2^31 - 1 workgroups per image or n > 65535 are MH_ERR_UNSUPPORTED (nothing is launched);
+ * offsets are 64-bit, n D H W is not otherwise limited.
+ * mh_median_filter_accepts: host arithmetic only -- 0: not supported, 1: radii (1, 1, 1) or (0, 1, 1), selected in registers by a min / max /
+ * median-of-3 network, 2: any other radii, a bisection over order-preserving keys counted from an LDS tile. */
+int mh_median_filter_accepts(int D, int H, int W, int rz, int ry, int rx);
+int mh_median_filter_f32(const float* src, float* dst, int n, int D, int H, int W, int rz, int ry, int rx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

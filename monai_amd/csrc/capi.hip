@@ -28,6 +28,7 @@
 #include "kernels/ccl.h"
 #include "kernels/preproc.h"
 #include "kernels/select.h"
+#include "kernels/median.h"
 #include "kernels/nn_simple.h"
 #include "kernels/conv1x1_h2.h"
 #include "kernels/resample.h"
@@ -2155,6 +2156,69 @@ int mh_cc_filter(const void* src, void* dst, int dtype, int64_t n, const double*
     MH_CC_DTYPE(dtype, MH_CC_FILTER)
 #undef MH_CC_FILTER
     return launched("cc_filter");
+}
+
+// ------------------------------------------------------------------------------------------ median filter (median.h)
+struct MedianPlan { int path; int la, lb; long long tiles_x, tiles_y, tiles_z; };
+
+// 0: not supported (why: *why), 1: median3_kernel, 2: median_general_kernel.  Host arithmetic only.
+static int median_plan(int D, int H, int W, int rz, int ry, int rx, MedianPlan& p, const char** why) {
+    p.path = 0;
+    if (D < 1 || H < 1 || W < 1 || rz < 0 || ry < 0 || rx < 0) { *why = "sizes must be positive and radii non-negative"; return 0; }
+    if (rz > MED_MAX_WINDOW || ry > MED_MAX_WINDOW || rx > MED_MAX_WINDOW || (2LL * rz + 1) * (2 * ry + 1) * (2 * rx + 1) > MED_MAX_WINDOW) {
+        *why = "windows of more than 343 values are not supported";
+        return 0;
+    }
+    int tx, ty, tz;
+    if (rx == 1 && ry == 1 && rz <= 1) {
+        p.path = 1; p.la = p.lb = 0;
+        tx = MED_TX; ty = rz ? 64 : 256; tz = rz ? 4 : 1;
+    } else {
+        long long best = -1;
+        for (int a = 8; a >= 0; --a)            // ties: the longest rows
+            for (int b = 8 - a; b >= 0; --b) {
+                const long long v = ((1LL << a) + 2 * rx) * ((1LL << b) + 2 * ry) * ((1LL << (8 - a - b)) + 2 * rz);
+                if (best < 0 || v < best) { best = v; p.la = a; p.lb = b; }
+            }
+        if (best > MED_GEN_LDS) { *why = "the staged tile does not fit"; return 0; }      // not reached for windows <= 343 (1960 keys at most)
+        p.path = 2;
+        tx = 1 << p.la; ty = 1 << p.lb; tz = 256 >> (p.la + p.lb);
+    }
+    p.tiles_x = ((long long)W + tx - 1) / tx; p.tiles_y = ((long long)H + ty - 1) / ty; p.tiles_z = ((long long)D + tz - 1) / tz;
+    if (p.tiles_x * p.tiles_y > 0x7fffffffLL || p.tiles_x * p.tiles_y * p.tiles_z > 0x7fffffffLL) {
+        p.path = 0;
+        *why = "more than 2^31 - 1 workgroups per image";
+        return 0;
+    }
+    return p.path;
+}
+
+int mh_median_filter_accepts(int D, int H, int W, int rz, int ry, int rx) {
+    MedianPlan p;
+    const char* why = "";
+    return median_plan(D, H, W, rz, ry, rx, p, &why);
+}
+
+int mh_median_filter_f32(const float* src, float* dst, int n, int D, int H, int W, int rz, int ry, int rx, void* stream) {
+    if (!src || !dst || n < 1 || D < 1 || H < 1 || W < 1) return fail(MH_ERR_ARG, "median_filter: bad argument");
+    if (rz < 0 || ry < 0 || rx < 0) return fail(MH_ERR_ARG, "median_filter: negative radius (%d, %d, %d)", rz, ry, rx);
+    if (src == dst) return fail(MH_ERR_ARG, "median_filter: src and dst must not be the same buffer (every output reads its neighbours' inputs)");
+    MedianPlan p;
+    const char* why = "";
+    if (!median_plan(D, H, W, rz, ry, rx, p, &why))
+        return fail(MH_ERR_UNSUPPORTED, "median_filter: %s (volume %d x %d x %d, window %d x %d x %d)", why, D, H, W, 2 * rz + 1, 2 * ry + 1, 2 * rx + 1);
+    if (n > 65535) return fail(MH_ERR_UNSUPPORTED, "median_filter: more than 65535 images per call (n = %d)", n);
+    const dim3 grid((unsigned)(p.tiles_x * p.tiles_y * p.tiles_z), (unsigned)n);
+    if (p.path == 1) {
+        const int vec = W % 4 == 0 && aligned(dst, 16);
+        if (rz) hipLaunchKernelGGL(median3_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, D, H, W, (int)p.tiles_x, (int)p.tiles_y, vec);
+        else hipLaunchKernelGGL(median3_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, D, H, W, (int)p.tiles_x, (int)p.tiles_y, vec);
+    } else {
+        MedGeneral g;
+        g.D = D; g.H = H; g.W = W; g.rz = rz; g.ry = ry; g.rx = rx; g.la = p.la; g.lb = p.lb; g.tiles_x = (int)p.tiles_x; g.tiles_y = (int)p.tiles_y;
+        hipLaunchKernelGGL(median_general_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, dst, g);
+    }
+    return launched("median_filter");
 }
 
 // ------------------------------------------------------------------------------------------ Gaussian smoothing

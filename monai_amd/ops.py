@@ -634,6 +634,54 @@ def separable_filter3d(src: torch.Tensor, kernels) -> torch.Tensor:
     return out
 
 
+MEDIAN_MAX_WINDOW = 343      # MED_MAX_WINDOW of csrc/kernels/median.h
+
+
+def median_filter_path(spatial_shape: Sequence[int], radius: Sequence[int]) -> int:
+    """Which kernel serves a median filter of ``radius`` (one value per axis) on images of ``spatial_shape`` (1 to 3 axes): 0 none, 1 the
+    register selection network (radius 1 on the last two axes, 0 or 1 on the first of three), 2 the general bisection kernel.  Host arithmetic."""
+    pad = 3 - len(spatial_shape)
+    dims, rad = (1,) * pad + tuple(int(v) for v in spatial_shape), (0,) * pad + tuple(int(v) for v in radius)
+    return _lib.lib().query("mh_median_filter_accepts", *dims, *rad)
+
+
+def median_filter(x: torch.Tensor, radius, spatial_dims: int = 3, passes: int = 1) -> torch.Tensor:
+    """Median of ``x`` over a box window of ``radius`` (an int or one per spatial axis) along its last ``spatial_dims`` axes, replicate padding, every
+    leading axis a batch -- what ``median_filter`` / ``MedianFilter`` of monai/networks/layers/simplelayers.py:441-539 compute, as one exact selection
+    kernel per pass: the volume is read once, no workspace grows with the window (the reference writes every voxel's whole window out first).
+    Finite inputs give the reference's bits; a selected ``-0.0`` comes out as ``+0.0`` and a window that holds ``inf`` / ``NaN`` gives ``NaN``, as
+    there.  ``passes`` repeats the filter between two buffers without host synchronisation.  A float32 device tensor; windows of at most 343 values."""
+    if spatial_dims not in (1, 2, 3):
+        raise _lib.UnsupportedOnDevice(f"monai_amd.median_filter: spatial_dims {spatial_dims} is not on the HIP path (1, 2 and 3 are)")
+    _lib.require_device(x)
+    if x.dim() < spatial_dims:
+        raise RuntimeError(f"monai_amd.median_filter: a tensor of at least {spatial_dims} axes required, got shape {tuple(x.shape)}")
+    rad = [int(r) for r in radius] if hasattr(radius, "__len__") else [int(radius)] * spatial_dims
+    if len(rad) != spatial_dims or any(r < 0 for r in rad):
+        raise ValueError(f"radius must be {spatial_dims} non-negative integers, got {radius}.")
+    window = 1
+    for r in rad:
+        window *= 2 * r + 1
+    if window > MEDIAN_MAX_WINDOW:
+        raise _lib.UnsupportedOnDevice(f"monai_amd.median_filter: a window of {window} values is not on the HIP path (at most {MEDIAN_MAX_WINDOW})")
+    src = x.contiguous()
+    if not src.numel() or passes < 1:
+        return src.clone()
+    dims = (1,) * (3 - spatial_dims) + tuple(src.shape[src.dim() - spatial_dims:])
+    rad = [0] * (3 - spatial_dims) + rad
+    n = src.numel() // (dims[0] * dims[1] * dims[2])
+    L = _lib.lib()
+    bufs = [torch.empty_like(src), torch.empty_like(src) if passes > 1 else None]
+    for i in range(int(passes)):
+        dst = bufs[i % 2]
+        try:
+            L.call("mh_median_filter_f32", _lib.ptr(src), _lib.ptr(dst), n, *dims, *rad, _s(x))
+        except _lib.KernelRejected as e:
+            raise _lib.UnsupportedOnDevice(str(e)) from None
+        src = dst
+    return src
+
+
 def add_act(a, a_nrm, b, b_nrm, slope: float, out, out_nrm=None):
     """out = leaky_relu(act(a) + act(b), slope) -- residual join of UnetResBlock.  out_nrm: `nrm_identity` records of `out` (magnitude bound)."""
     _lib.require_device(a, a_nrm, b, b_nrm, out, out_nrm)

@@ -68,7 +68,7 @@ _TARGETS = {
         "ScaleIntensityRange": ("monai_amd.transforms.intensity.array", "ScaleIntensityRange"),
         "NormalizeIntensity": ("monai_amd.transforms.intensity.array", "NormalizeIntensity"),
         "ScaleIntensity": ("monai_amd.transforms.intensity.array", "ScaleIntensity"),
-        **{n: ("monai_amd.transforms.intensity.array", n) for n in ("ScaleIntensityRangePercentiles", "ClipIntensityPercentiles")},
+        **{n: ("monai_amd.transforms.intensity.array", n) for n in ("ScaleIntensityRangePercentiles", "ClipIntensityPercentiles", "MedianSmooth")},
     },
     "monai.transforms.croppad.array": {n: ("monai_amd.transforms.croppad.array", n) for n in
                                        ("CropForeground", "Pad", "SpatialPad", "BorderPad", "DivisiblePad", "Crop", "SpatialCrop", "CenterSpatialCrop")},
@@ -111,7 +111,7 @@ _TARGETS = {
         "ScaleIntensityd": ("monai_amd.transforms.intensity.dictionary", "ScaleIntensityd"),
         "ScaleIntensityD": ("monai_amd.transforms.intensity.dictionary", "ScaleIntensityd"),
         "ScaleIntensityDict": ("monai_amd.transforms.intensity.dictionary", "ScaleIntensityd"),
-        **{n + suffix: ("monai_amd.transforms.intensity.dictionary", n + "d") for n in ("ScaleIntensityRangePercentiles", "ClipIntensityPercentiles")
+        **{n + suffix: ("monai_amd.transforms.intensity.dictionary", n + "d") for n in ("ScaleIntensityRangePercentiles", "ClipIntensityPercentiles", "MedianSmooth")
            for suffix in ("d", "D", "Dict")},
     },
     "monai.networks.layers.spatial_transforms": {
@@ -121,7 +121,7 @@ _TARGETS = {
         "grid_count": ("monai_amd.networks.layers.spatial_transforms", "grid_count"),
         "grid_grad": ("monai_amd.networks.layers.spatial_transforms", "grid_grad"),
     },
-    "monai.networks.layers.simplelayers": {"GaussianFilter": ("monai_amd.networks.layers.simplelayers", "GaussianFilter")},
+    "monai.networks.layers.simplelayers": {n: ("monai_amd.networks.layers.simplelayers", n) for n in ("GaussianFilter", "MedianFilter", "median_filter")},
     "monai.networks.blocks.warp": {"Warp": ("monai_amd.networks.blocks.warp", "Warp"), "DVF2DDF": ("monai_amd.networks.blocks.warp", "DVF2DDF")},
     "monai.metrics.meandice": {n: ("monai_amd.metrics.meandice", n) for n in ("DiceMetric", "compute_dice", "DiceHelper")},
     "monai.metrics.meaniou": {n: ("monai_amd.metrics.meaniou", n) for n in ("MeanIoU", "compute_iou")},

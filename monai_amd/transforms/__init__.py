@@ -8,6 +8,7 @@ from .intensity import (  # noqa: F401
     NormalizeIntensityd, ScaleIntensity, ScaleIntensityD, ScaleIntensityDict, ScaleIntensityd, ScaleIntensityRange, ScaleIntensityRangeD, ScaleIntensityRangeDict,
     ScaleIntensityRanged,
 )
+from .intensity import MedianSmooth, MedianSmoothD, MedianSmoothDict, MedianSmoothd  # noqa: F401
 from .intensity import ClipIntensityPercentiles, ClipIntensityPercentilesD, ClipIntensityPercentilesDict, ClipIntensityPercentilesd  # noqa: F401
 from .intensity import (  # noqa: F401
     ScaleIntensityRangePercentiles, ScaleIntensityRangePercentilesD, ScaleIntensityRangePercentilesDict, ScaleIntensityRangePercentilesd,

@@ -1,4 +1,5 @@
-"""``GaussianSmooth`` (monai/transforms/intensity/array.py:1590-1622, the fused smoothing kernel), ``ScaleIntensityRange``
+"""``GaussianSmooth`` (monai/transforms/intensity/array.py:1590-1622, the fused smoothing kernel), ``MedianSmooth`` (array.py:1561-1587,
+the exact median-filter kernel), ``ScaleIntensityRange``
 (array.py:958-1012, one element-wise pass), ``NormalizeIntensity``, ``ScaleIntensity`` and the percentile transforms
 ``ScaleIntensityRangePercentiles`` (array.py:1299-1418) and ``ClipIntensityPercentiles`` (array.py:1015-1157) on the exact
 order-statistic kernel."""
@@ -11,9 +12,10 @@ import numpy as np
 import torch
 
 from ...data.meta_tensor import is_meta
-from ...networks.layers.simplelayers import GaussianFilter
+from ...networks.layers.simplelayers import GaussianFilter, MedianFilter
+from ...utils.misc import ensure_tuple_rep
 
-__all__ = ["GaussianSmooth", "ScaleIntensityRange", "NormalizeIntensity", "ScaleIntensity", "ScaleIntensityRangePercentiles", "ClipIntensityPercentiles"]
+__all__ = ["GaussianSmooth", "MedianSmooth", "ScaleIntensityRange", "NormalizeIntensity", "ScaleIntensity", "ScaleIntensityRangePercentiles", "ClipIntensityPercentiles"]
 
 
 class GaussianSmooth:
@@ -27,6 +29,25 @@ class GaussianSmooth:
         x = data.to(torch.float)
         sigma = list(self.sigma) if isinstance(self.sigma, Sequence) else self.sigma
         out = GaussianFilter(x.ndim - 1, sigma, approx=self.approx)(x.unsqueeze(0)).squeeze(0)
+        if is_meta(img):
+            return type(img)(out, meta=dict(img.meta), applied_operations=list(getattr(img, "applied_operations", [])))
+        return out
+
+
+class MedianSmooth:
+    """``monai.transforms.MedianSmooth`` (monai/transforms/intensity/array.py:1561-1587): median filter of a channel-first image over a box of
+    ``radius`` (a scalar or one value per spatial axis), replicate padding, on the exact selection kernel (csrc/kernels/median.h) -- one pass
+    over the image, where the reference writes every voxel's whole window out before ``torch.median``.  The image is converted to float32,
+    as there; finite inputs give the reference's bits."""
+
+    def __init__(self, radius: Sequence[int] | int = 1) -> None:
+        self.radius = radius
+
+    def __call__(self, img):
+        data = img.as_tensor() if is_meta(img) else torch.as_tensor(img)
+        x = data.to(torch.float)
+        spatial_dims = x.ndim - 1
+        out = MedianFilter(ensure_tuple_rep(self.radius, spatial_dims), spatial_dims=spatial_dims)(x)
         if is_meta(img):
             return type(img)(out, meta=dict(img.meta), applied_operations=list(getattr(img, "applied_operations", [])))
         return out

@@ -1,16 +1,17 @@
-"""``GaussianSmoothd`` (monai/transforms/intensity/dictionary.py:1184-1216) and ``ScaleIntensityRanged`` (dictionary.py:855-892)."""
+"""``GaussianSmoothd`` (monai/transforms/intensity/dictionary.py:1184-1216), ``MedianSmoothd`` (dictionary.py:1157-1181) and ``ScaleIntensityRanged``
+(dictionary.py:855-892)."""
 
 from __future__ import annotations
 
 import numpy as np
 
 from ...utils.misc import ensure_tuple
-from .array import ClipIntensityPercentiles, GaussianSmooth, NormalizeIntensity, ScaleIntensity, ScaleIntensityRange, ScaleIntensityRangePercentiles
+from .array import ClipIntensityPercentiles, GaussianSmooth, MedianSmooth, NormalizeIntensity, ScaleIntensity, ScaleIntensityRange, ScaleIntensityRangePercentiles
 
 __all__ = ["GaussianSmoothd", "GaussianSmoothD", "GaussianSmoothDict", "ScaleIntensityRanged", "ScaleIntensityRangeD", "ScaleIntensityRangeDict",
            "NormalizeIntensityd", "NormalizeIntensityD", "NormalizeIntensityDict", "ScaleIntensityd", "ScaleIntensityD", "ScaleIntensityDict",
            "ScaleIntensityRangePercentilesd", "ScaleIntensityRangePercentilesD", "ScaleIntensityRangePercentilesDict",
-           "ClipIntensityPercentilesd", "ClipIntensityPercentilesD", "ClipIntensityPercentilesDict"]
+           "ClipIntensityPercentilesd", "ClipIntensityPercentilesD", "ClipIntensityPercentilesDict", "MedianSmoothd", "MedianSmoothD", "MedianSmoothDict"]
 
 
 class GaussianSmoothd:
@@ -94,3 +95,15 @@ class ClipIntensityPercentilesd(GaussianSmoothd):
 
 
 ClipIntensityPercentilesD = ClipIntensityPercentilesDict = ClipIntensityPercentilesd
+
+
+class MedianSmoothd(GaussianSmoothd):
+    """Dictionary version of :class:`MedianSmooth` (monai/transforms/intensity/dictionary.py:1157-1181)."""
+
+    def __init__(self, keys, radius, allow_missing_keys: bool = False) -> None:
+        self.keys = ensure_tuple(keys)
+        self.allow_missing_keys = allow_missing_keys
+        self.converter = MedianSmooth(radius)
+
+
+MedianSmoothD = MedianSmoothDict = MedianSmoothd
