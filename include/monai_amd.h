@@ -647,6 +647,35 @@ int mh_separable_filter3d_f32(const float* src, float* dst, int NC, int D, int H
 int mh_median_filter_accepts(int D, int H, int W, int rz, int ry, int rx);
 int mh_median_filter_f32(const float* src, float* dst, int n, int D, int H, int W, int rz, int ry, int rx, void* stream);
 
+/* ---- Spline-order resampling, orders 0-5 (integer `mode` of Spacing / SpatialResample / Resample / lazy resampling) --------- */
+
+/* What scipy.ndimage.map_coordinates(c, coords, order, mode, cval = 0.0, prefilter = True) computes per channel of a float image -- the numpy
+ * branch of the reference's Resample (monai/transforms/spatial/array.py:2092-2100).  `mode` is one of MH_SPLINE_*; `rank` is 3, or 2 for images
+ * [NC][1][H][W] whose leading axis is absent (no pad, no filter pass, one tap of weight 1).  Orders outside 0..5 fail with scipy's own message,
+ * "spline order not supported"; every argument is checked before anything is launched.
+ *
+ * mh_spline_prefilter_f64 (orders 2-5): fp32 image -> fp64 B-spline coefficients [NC][D'][H'][W'], one recursive pass per present axis; `nearest`
+ * and `grid-constant` filter the image padded by 12 samples per side of every present axis (edge values / zeros; D' = D + 24, ...), the other
+ * modes keep the extents.  mh_spline_workspace_bytes is that buffer's size (0 for orders 0 and 1), host arithmetic only.
+ * mh_spline_resample_affine_f32 / _grid_f32: `vol` is the coefficient buffer for orders 2-5 and the fp32 image itself for orders 0 and 1; the
+ * image index of output voxel (oz, oy, ox) is m @ (oz, oy, ox, 1) (m: 3 x 4 fp64 on the host), or scale[a] * coords[a] + offset[a] of a dense
+ * grid [3][Do][Ho][Wo] (fp32 or fp64).  fp64 arithmetic, one rounding to fp32; a non-finite coordinate writes NaN.  No atomics, 64-bit offsets,
+ * the same bits on every run. */
+#define MH_SPLINE_REFLECT 0
+#define MH_SPLINE_GRID_MIRROR 1
+#define MH_SPLINE_CONSTANT 2
+#define MH_SPLINE_GRID_CONSTANT 3
+#define MH_SPLINE_NEAREST 4
+#define MH_SPLINE_MIRROR 5
+#define MH_SPLINE_GRID_WRAP 6
+#define MH_SPLINE_WRAP 7
+int64_t mh_spline_workspace_bytes(int order, int mode, int rank, int NC, int D, int H, int W);
+int mh_spline_prefilter_f64(const float* src, double* coef, int NC, int rank, int D, int H, int W, int order, int mode, void* stream);
+int mh_spline_resample_affine_f32(const void* vol, int NC, int rank, int Di, int Hi, int Wi, float* dst, int Do, int Ho, int Wo, const double* m,
+                                  int order, int mode, void* stream);
+int mh_spline_resample_grid_f32(const void* vol, int NC, int rank, int Di, int Hi, int Wi, const void* coords, int coords_f64, const double* scale3,
+                                const double* offset3, float* dst, int Do, int Ho, int Wo, int order, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

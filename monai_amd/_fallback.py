@@ -3,7 +3,7 @@ path -- never fail a previously valid call").
 
 The MI355X classes cover the hot path: fp32 tensors resident in HBM, 3-D windows, the common network configurations,
 inference.  Everything else the reference accepts -- CPU tensors and numpy arrays, training mode (autograd), 2-D networks, other
-norms / activations / up-sampling modes, spline interpolation orders, half / double precision -- is NOT re-implemented here;
+norms / activations / up-sampling modes, half / double precision -- is NOT re-implemented here;
 when MONAI is importable such a call is handed to the reference's own class / function instead of raising:
 
   * constructor time: ``OurClass(*args)`` whose configuration the HIP path does not cover (it raises ``NotImplementedError``)

@@ -29,6 +29,7 @@
 #include "kernels/preproc.h"
 #include "kernels/select.h"
 #include "kernels/median.h"
+#include "kernels/spline.h"
 #include "kernels/nn_simple.h"
 #include "kernels/conv1x1_h2.h"
 #include "kernels/resample.h"
@@ -2219,6 +2220,118 @@ int mh_median_filter_f32(const float* src, float* dst, int n, int D, int H, int 
         hipLaunchKernelGGL(median_general_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, dst, g);
     }
     return launched("median_filter");
+}
+
+// ------------------------------------------------------------------------------------------ spline-order resampling (orders 0-5)
+static int spline_geom(SplineGeom& g, const char* what, int NC, int rank, int D, int H, int W, int order, int mode) {
+    if (order < 0 || order > 5) return fail(MH_ERR_ARG, "spline order not supported");
+    if (mode < 0 || mode >= SP_NUM_MODES) return fail(MH_ERR_ARG, "%s: unknown boundary mode %d", what, mode);
+    if (rank != 2 && rank != 3) return fail(MH_ERR_ARG, "%s: images of 2 or 3 spatial axes (got rank %d)", what, rank);
+    if (NC < 1 || D < 1 || H < 1 || W < 1) return fail(MH_ERR_ARG, "%s: bad shape (%d, %d, %d, %d)", what, NC, D, H, W);
+    if (rank == 2 && D != 1) return fail(MH_ERR_ARG, "%s: a 2-D image is [NC][1][H][W] (got D = %d)", what, D);
+    const int padded = order > 1 && (mode == SP_NEAREST || mode == SP_GRID_CONSTANT);
+    g.NC = NC;
+    g.n[0] = D; g.n[1] = H; g.n[2] = W;
+    for (int a = 0; a < 3; ++a) {
+        g.present[a] = a >= 3 - rank;
+        g.pad[a] = (padded && g.present[a]) ? SP_NPAD : 0;
+        if (g.n[a] > 0x7fffffff - 2 * SP_NPAD - 64) return fail(MH_ERR_UNSUPPORTED, "%s: an axis of %d samples", what, g.n[a]);
+        g.N[a] = g.n[a] + 2 * g.pad[a];
+    }
+    return MH_OK;
+}
+
+int64_t mh_spline_workspace_bytes(int order, int mode, int rank, int NC, int D, int H, int W) {
+    SplineGeom g;
+    if (int e = spline_geom(g, "spline_workspace_bytes", NC, rank, D, H, W, order, mode)) return e;
+    if (order < 2) return 0;
+    return (int64_t)NC * g.N[0] * g.N[1] * g.N[2] * (int64_t)sizeof(double);
+}
+
+int mh_spline_prefilter_f64(const float* src, double* coef, int NC, int rank, int D, int H, int W, int order, int mode, void* stream) {
+    SplineFilterArgs a;
+    if (int e = spline_geom(a.g, "spline_prefilter", NC, rank, D, H, W, order, mode)) return e;
+    if (!src || !coef) return fail(MH_ERR_ARG, "spline_prefilter: null pointer");
+    if (order < 2) return fail(MH_ERR_ARG, "spline_prefilter: orders 0 and 1 have no prefilter (order %d)", order);
+    // poles of the B-spline of this order (Unser, Aldroubi, Eden 1993), the expressions scipy evaluates
+    a.npoles = order < 4 ? 1 : 2;
+    a.pole[1] = 0.0;
+    switch (order) {
+        case 2: a.pole[0] = sqrt(8.0) - 3.0; break;
+        case 3: a.pole[0] = sqrt(3.0) - 2.0; break;
+        case 4: a.pole[0] = sqrt(664.0 - sqrt(438976.0)) + sqrt(304.0) - 19.0; a.pole[1] = sqrt(664.0 + sqrt(438976.0)) - sqrt(304.0) - 19.0; break;
+        default: a.pole[0] = sqrt(67.5 - sqrt(4436.25)) + sqrt(26.25) - 6.5; a.pole[1] = sqrt(67.5 + sqrt(4436.25)) - sqrt(26.25) - 6.5; break;
+    }
+    a.gain = 1.0;
+    for (int p = 0; p < a.npoles; ++p) a.gain *= (1.0 - a.pole[p]) * (1.0 - 1.0 / a.pole[p]);
+    a.ext = (mode == SP_REFLECT || mode == SP_GRID_MIRROR || mode == SP_NEAREST) ? SPX_HALF : (mode == SP_GRID_WRAP ? SPX_PERIODIC : SPX_WHOLE);
+    a.zero_fill = mode == SP_GRID_CONSTANT;
+    int axes[3], na = 0;
+    for (int ax = 2; ax >= 0; --ax)
+        if (a.g.present[ax] && a.g.N[ax] > 1) axes[na++] = ax;
+    if (na == 0) axes[na++] = 2;          // a one-voxel image: the cast alone
+    for (int i = 0; i < na; ++i) {
+        const int ax = axes[i];
+        const long long lines = (long long)NC * a.g.N[ax == 0 ? 1 : 0] * a.g.N[ax == 2 ? 1 : 2];
+        if (lines > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "spline_prefilter: problem too large for one launch");
+    }
+    for (int i = 0; i < na; ++i) {
+        a.axis = axes[i];
+        const long long lines = (long long)NC * a.g.N[a.axis == 0 ? 1 : 0] * a.g.N[a.axis == 2 ? 1 : 2];
+        if (i == 0) hipLaunchKernelGGL(spline_prefilter_kernel<true>, dim3(blocks_for(lines)), dim3(256), 0, (hipStream_t)stream, src, coef, a);
+        else hipLaunchKernelGGL(spline_prefilter_kernel<false>, dim3(blocks_for(lines)), dim3(256), 0, (hipStream_t)stream, src, coef, a);
+    }
+    return launched("spline_prefilter");
+}
+
+template <bool GRID, typename TG>
+static int spline_launch(const void* vol, const TG* grid, float* dst, const SplineSampleArgs& a, hipStream_t s) {
+    const unsigned nb = blocks_for((long long)a.Do * a.Ho * a.Wo);
+#define MH_SP(O_, T_) hipLaunchKernelGGL((spline_resample_kernel<O_, T_, TG, GRID>), dim3(nb), dim3(256), 0, s, static_cast<const T_*>(vol), grid, dst, a)
+    switch (a.order) {
+        case 0: MH_SP(0, float); break;
+        case 1: MH_SP(1, float); break;
+        case 2: MH_SP(2, double); break;
+        case 3: MH_SP(3, double); break;
+        case 4: MH_SP(4, double); break;
+        default: MH_SP(5, double); break;
+    }
+#undef MH_SP
+    return launched("spline_resample");
+}
+
+static int spline_sample_args(SplineSampleArgs& a, const char* what, const void* vol, int NC, int rank, int Di, int Hi, int Wi, const float* dst, int Do, int Ho, int Wo,
+                              int order, int mode) {
+    if (int e = spline_geom(a.g, what, NC, rank, Di, Hi, Wi, order, mode)) return e;
+    if (!vol || !dst) return fail(MH_ERR_ARG, "%s: null pointer", what);
+    if (Do < 1 || Ho < 1 || Wo < 1) return fail(MH_ERR_ARG, "%s: bad output shape (%d, %d, %d)", what, Do, Ho, Wo);
+    if ((long long)Do * Ho * Wo > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "%s: problem too large for one launch", what);
+    a.Do = Do; a.Ho = Ho; a.Wo = Wo; a.order = order; a.mode = mode;
+    for (int i = 0; i < 12; ++i) a.m[i] = 0.0;
+    for (int i = 0; i < 3; ++i) { a.ga[i] = 1.0; a.gb[i] = 0.0; }
+    return MH_OK;
+}
+
+int mh_spline_resample_affine_f32(const void* vol, int NC, int rank, int Di, int Hi, int Wi, float* dst, int Do, int Ho, int Wo, const double* m,
+                                  int order, int mode, void* stream) {
+    SplineSampleArgs a;
+    if (int e = spline_sample_args(a, "spline_resample_affine", vol, NC, rank, Di, Hi, Wi, dst, Do, Ho, Wo, order, mode)) return e;
+    if (!m) return fail(MH_ERR_ARG, "spline_resample_affine: null matrix");
+    for (int i = 0; i < 12; ++i) a.m[i] = m[i];
+    return spline_launch<false, double>(vol, nullptr, dst, a, (hipStream_t)stream);
+}
+
+int mh_spline_resample_grid_f32(const void* vol, int NC, int rank, int Di, int Hi, int Wi, const void* coords, int coords_f64, const double* scale3,
+                                const double* offset3, float* dst, int Do, int Ho, int Wo, int order, int mode, void* stream) {
+    SplineSampleArgs a;
+    if (int e = spline_sample_args(a, "spline_resample_grid", vol, NC, rank, Di, Hi, Wi, dst, Do, Ho, Wo, order, mode)) return e;
+    if (!coords) return fail(MH_ERR_ARG, "spline_resample_grid: null grid");
+    for (int i = 0; i < 3; ++i) {
+        if (scale3) a.ga[i] = scale3[i];
+        if (offset3) a.gb[i] = offset3[i];
+    }
+    if (coords_f64) return spline_launch<true, double>(vol, static_cast<const double*>(coords), dst, a, (hipStream_t)stream);
+    return spline_launch<true, float>(vol, static_cast<const float*>(coords), dst, a, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------ Gaussian smoothing

@@ -682,6 +682,74 @@ def median_filter(x: torch.Tensor, radius, spatial_dims: int = 3, passes: int = 
     return src
 
 
+SPLINE_MODES = {"reflect": 0, "grid-mirror": 1, "constant": 2, "grid-constant": 3, "nearest": 4, "mirror": 5, "grid-wrap": 6, "wrap": 7}      # MH_SPLINE_*
+# coefficients of at most this many bytes exist at a time (fp64, per channel 8 B x the padded volume: 1.0-1.25 GiB for one 512^3 channel); more channels
+# than fit are resampled in groups, each with its own prefilter and sampling launch
+SPLINE_WORKSPACE_BYTES = 2 << 30
+
+
+def _spline_args(x: torch.Tensor, order, mode: str):
+    _lib.require_device(x)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise RuntimeError("monai_amd.spline: the image must be a contiguous [NC, D, H, W] tensor")
+    if mode not in SPLINE_MODES:
+        raise ValueError(f"Unsupported padding mode: {mode}, available options are {sorted(SPLINE_MODES)}.")
+    return int(order), SPLINE_MODES[mode]
+
+
+def spline_prefilter(x: torch.Tensor, order: int, mode: str = "mirror", rank: int = 3) -> torch.Tensor:
+    """B-spline coefficients of ``x`` [NC, D, H, W] (float32) as float64 -- ``scipy.ndimage.spline_filter(pad(c), order, mode=mode, output=float64)``
+    per channel, where ``nearest`` and ``grid-constant`` pad every axis by 12 samples first (as ``map_coordinates`` does) and the other modes do
+    not.  ``rank=2``: images [NC, 1, H, W] whose leading axis is absent.  Orders 2 to 5."""
+    o, m = _spline_args(x, order, mode)
+    nc, d, h, w = (int(v) for v in x.shape)
+    L = _lib.lib()
+    nbytes = L.query("mh_spline_workspace_bytes", o, m, int(rank), nc, d, h, w)
+    pad = 12 if (mode in ("nearest", "grid-constant") and o > 1) else 0
+    shape = (nc, d + (2 * pad if rank == 3 else 0), h + 2 * pad, w + 2 * pad)
+    coef = torch.empty(shape, dtype=torch.float64, device=x.device)
+    assert coef.numel() * 8 == nbytes or o < 2, (shape, nbytes)
+    L.call("mh_spline_prefilter_f64", _lib.ptr(x), _lib.ptr(coef), nc, int(rank), d, h, w, o, m, _s(x))
+    return coef
+
+
+def spline_resample(x: torch.Tensor, order: int, mode: str, out_size: Sequence[int] | None = None, m=None, coords: torch.Tensor | None = None,
+                    scale=(1.0, 1.0, 1.0), offset=(0.0, 0.0, 0.0), rank: int = 3) -> torch.Tensor:
+    """``scipy.ndimage.map_coordinates(c, coordinates, order=order, mode=mode)`` for every channel ``c`` of ``x`` [NC, D, H, W] (float32) -> float32
+    [NC, Do, Ho, Wo].  The coordinates are either affine, ``index = m @ (oz, oy, ox, 1)`` with ``m`` 3 x 4 (float64, host) and ``out_size``, or a dense
+    grid ``coords`` [3, Do, Ho, Wo] (float32 / float64) with ``index[a] = scale[a] * coords[a] + offset[a]``.  Orders 2-5 prefilter into float64
+    coefficients first (`spline_prefilter`), at most ``SPLINE_WORKSPACE_BYTES`` of them at a time."""
+    o, md = _spline_args(x, order, mode)
+    nc, d, h, w = (int(v) for v in x.shape)
+    L = _lib.lib()
+    if (m is None) == (coords is None):
+        raise ValueError("monai_amd.spline_resample: either an index matrix `m` with `out_size` or a coordinate grid `coords`")
+    if coords is not None:
+        _lib.require_device(coords, dtypes=(torch.float32, torch.float64))
+        if coords.dim() != 4 or coords.shape[0] != 3 or not coords.is_contiguous():
+            raise RuntimeError("monai_amd.spline_resample: coords must be a contiguous [3, Do, Ho, Wo] tensor")
+        do, ho, wo = (int(v) for v in coords.shape[1:])
+        sc = (C.c_double * 3)(*[float(v) for v in scale])
+        of = (C.c_double * 3)(*[float(v) for v in offset])
+    else:
+        do, ho, wo = (int(v) for v in out_size)
+        mm = (C.c_double * 12)(*[float(v) for v in m])
+    per_channel = L.query("mh_spline_workspace_bytes", o, md, int(rank), 1, d, h, w)          # also the order / mode / shape check, before any allocation
+    out = torch.empty((nc, do, ho, wo), dtype=torch.float32, device=x.device)
+    if not out.numel():
+        return out
+    group = nc if per_channel == 0 else max(1, min(nc, SPLINE_WORKSPACE_BYTES // per_channel))
+    for c0 in range(0, nc, group):
+        xs, os_ = x[c0:c0 + group], out[c0:c0 + group]
+        vol = xs if o < 2 else spline_prefilter(xs, o, mode, rank)
+        if coords is not None:
+            L.call("mh_spline_resample_grid_f32", _lib.ptr(vol), int(xs.shape[0]), int(rank), d, h, w, _lib.ptr(coords), int(coords.dtype == torch.float64), sc, of,
+                   _lib.ptr(os_), do, ho, wo, o, md, _s(x))
+        else:
+            L.call("mh_spline_resample_affine_f32", _lib.ptr(vol), int(xs.shape[0]), int(rank), d, h, w, _lib.ptr(os_), do, ho, wo, mm, o, md, _s(x))
+    return out
+
+
 def add_act(a, a_nrm, b, b_nrm, slope: float, out, out_nrm=None):
     """out = leaky_relu(act(a) + act(b), slope) -- residual join of UnetResBlock.  out_nrm: `nrm_identity` records of `out` (magnitude bound)."""
     _lib.require_device(a, a_nrm, b, b_nrm, out, out_nrm)

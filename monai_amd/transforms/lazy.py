@@ -162,7 +162,8 @@ def resample(data, matrix, kwargs: dict | None = None):
 
     Pure axis operations (flip / permute / integer shift; `lazy_resample_mode` "auto", no align_corners): the exact gather kernels
     (`mh_flip_permute_f32`, `mh_crop_pad_f32`), zero padding.  Anything else: ONE `mh_affine_resample_f32` from the image's affine
-    to ``affine @ matrix`` at `lazy_shape`, bilinear / border unless `lazy_interpolation_mode` / `lazy_padding_mode` are given,
+    to ``affine @ matrix`` at `lazy_shape`, bilinear / border unless `lazy_interpolation_mode` / `lazy_padding_mode` are given (an integer
+    `lazy_interpolation_mode` is a spline order: one prefilter and one sampling launch of csrc/kernels/spline.h),
     float64 coordinates unless `lazy_dtype` says float32.  The result is float32 with the new affine."""
     from .. import ops
     from .croppad.array import _run_crop_pad
@@ -239,7 +240,9 @@ def resample(data, matrix, kwargs: dict | None = None):
                 y = torch.nn.functional.pad(y[None], pads, mode=pm)[0]
         return wrap(y.to(torch.float32))
 
-    interp = kwargs.get(LazyAttr.INTERP_MODE) or "bilinear"
+    interp = kwargs.get(LazyAttr.INTERP_MODE)
+    if interp is None or interp == "":      # not `or`: spline order 0 is a mode
+        interp = "bilinear"
     padding = kwargs.get(LazyAttr.PADDING_MODE) or "border"
     dt = kwargs.get(LazyAttr.DTYPE, torch.float64)
     dt = torch.float32 if dt in (torch.float32, np.float32, "float32") else torch.float64

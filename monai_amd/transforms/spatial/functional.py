@@ -15,11 +15,21 @@ from ...utils.misc import ensure_tuple, fall_back_tuple
 __all__ = ["spatial_resample"]
 
 
-def _mode_name(mode) -> str:
+def spline_order(mode):
+    """The spline order 0..5 when `mode` selects the reference's scipy branch -- an integer, an integer-valued enum or a digit string, what
+    ``resolves_modes(backend=None)`` looks up in ``SplineMode`` (monai/transforms/utils.py:2319-2328) -- else None."""
     m = getattr(mode, "value", mode)
-    if isinstance(m, (int, np.integer)) and not isinstance(m, bool):
-        raise NotImplementedError("monai_amd: spline-order (integer) interpolation modes use scipy in the reference and are not on the HIP path")
-    m = str(m).lower()
+    if isinstance(m, bool):
+        return None
+    if isinstance(m, (int, np.integer)):
+        return int(m) if 0 <= int(m) <= 5 else None
+    if isinstance(m, str) and len(m) == 1 and m in "012345":
+        return int(m)
+    return None
+
+
+def _mode_name(mode) -> str:
+    m = str(getattr(mode, "value", mode)).lower()
     if m in ("bilinear", "trilinear", "linear"):
         return "bilinear"
     if m == "nearest":
@@ -39,6 +49,44 @@ def _pad_name(padding_mode) -> str:
     if p not in ("zeros", "border", "reflection"):
         raise ValueError(f"Unsupported padding_mode: {padding_mode}, available options are {sorted(_NDIMAGE_PAD) + ['zeros', 'border', 'reflection']}.")
     return p
+
+
+# grid_sample padding names -> scipy.ndimage boundary modes, the table of the reference's `_to_numpy_resample_padding_mode` (monai/transforms/utils.py:2266-2278)
+_NDIMAGE_MODES = ("reflect", "grid-mirror", "constant", "grid-constant", "nearest", "mirror", "grid-wrap", "wrap")
+_TORCH_TO_NDIMAGE = {"zeros": "constant", "border": "nearest", "reflection": "reflect"}
+
+
+def _spline_pad_name(padding_mode) -> str:
+    p = str(getattr(padding_mode, "value", padding_mode)).lower()
+    p = _TORCH_TO_NDIMAGE.get(p, p)
+    if p not in _NDIMAGE_MODES:
+        raise ValueError(f"Unsupported padding_mode: {padding_mode}, available options are {sorted(_TORCH_TO_NDIMAGE) + list(_NDIMAGE_MODES)}.")
+    return p
+
+
+def spline_index_matrix(xform, in_size, out_size, align_corners: bool) -> np.ndarray:
+    """3 x 4 fp64 matrix M with  input index = M @ (output index, 1)  of the reference's integer-mode branch (functional.py:161-173): ``xform @
+    translate((d_out - 1) / 2)`` handed to ``Affine(normalized=True)``, whose ``AffineGrid`` applies it to the centred grid ``o - (d_out - 1) / 2``
+    (scaled by ``d / (d - 1)`` per output axis under align_corners, array.py:1775-1780) and whose ``Resample(norm_coords=False)`` leaves the result
+    alone, or maps it with ``(d_in - 1) / d_in * (g + 0.5)`` under align_corners (array.py:2076-2082).  2-D transforms get a leading zero row."""
+    xform = np.asarray(xform, dtype=np.float64)
+    r = len(xform) - 1
+    m = xform.copy()
+    if align_corners:
+        def translate(v):
+            t = np.eye(r + 1)
+            t[:r, -1] = v
+            return t
+
+        c_out = [(float(d) - 1.0) / 2.0 for d in out_size]
+        # the reference builds this scale with torch.as_tensor of Python floats (create_scale, transforms/utils.py:1016-1021): float32 values
+        s_out = np.diag([float(np.float32(max(int(d), 2) / (max(int(d), 2) - 1.0))) for d in out_size] + [1.0])
+        s_in = np.diag([(max(int(d), 2) - 1.0) / max(int(d), 2) for d in in_size] + [1.0])
+        m = s_in @ translate([0.5] * r) @ xform @ translate(c_out) @ s_out @ translate([-v for v in c_out])
+    full = np.zeros((3, 4))
+    full[3 - r:, 3 - r:3] = m[:r, :r]
+    full[3 - r:, 3] = m[:r, -1]
+    return full
 
 
 def spatial_resample(img, dst_affine, spatial_size, mode, padding_mode, align_corners, dtype_pt, transform_info=None):
@@ -121,6 +169,23 @@ def _execute_resample(data, xform, out_size, spatial_rank, mode, padding_mode, a
     _lib.require_device(x)
     if spatial_rank == 1:
         raise NotImplementedError("monai_amd: 1-D spatial_resample is not on the HIP path")
+    order = spline_order(mode)
+    if order is not None:
+        # the reference's scipy branch (functional.py:161-173): one prefilter and one sampling launch on float64 coefficients; `dtype_pt` only
+        # chooses the precision of the reference's coordinate grid, here the coordinates are fp64 either way
+        if data.dtype != torch.float32:
+            raise _lib.UnsupportedOnDevice(f"monai_amd: spline-order resampling of a {data.dtype} image is not on the HIP path (float32 is)")
+        ac = bool(align_corners) if align_corners not in (None, "none") else False
+        m = memo(("spline-index", _bytes(xform), tuple(int(v) for v in in_sp), tuple(int(v) for v in out_size), ac),
+                 lambda: spline_index_matrix(xform, in_sp, [int(v) for v in out_size], ac))
+        pad = 3 - spatial_rank
+        vol = x.reshape((x.shape[0],) + (1,) * pad + tuple(in_sp))
+        out = ops.spline_resample(vol, order, _spline_pad_name(padding_mode), out_size=(1,) * pad + tuple(int(v) for v in out_size), m=m.reshape(-1),
+                                  rank=spatial_rank)
+        out = out.reshape((x.shape[0],) + tuple(int(v) for v in out_size))
+        if extra:
+            out = out.reshape((chns, *[int(v) for v in out_size], *extra))
+        return out, xform, tuple(int(v) for v in out_size)
     m = memo(("index", _bytes(xform), tuple(int(v) for v in in_sp), tuple(int(v) for v in out_size), bool(align_corners)),
              lambda: index_matrix(xform, in_sp, [int(v) for v in out_size], normalized=False, align_corners=bool(align_corners), reverse_indexing=True))
     pad = 3 - spatial_rank
