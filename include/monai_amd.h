@@ -676,6 +676,26 @@ int mh_spline_resample_affine_f32(const void* vol, int NC, int rank, int Di, int
 int mh_spline_resample_grid_f32(const void* vol, int NC, int rank, int Di, int Hi, int Wi, const void* coords, int coords_f64, const double* scale3,
                                 const double* offset3, float* dst, int Do, int Ho, int Wo, int order, int mode, void* stream);
 
+/* ---- Exact bilateral filter (monai._C.bilateral_filter, fast_approx = False) ---------------------------------- */
+
+/* dst = the exact bilateral filter of src, B images of C channels [B][C][D][H][W] -- monai._C.bilateral_filter(input, spatial_sigma, color_sigma,
+ * fast_approx = False) (monai/csrc/ext.cpp:23, filtering/bilateral/bilateral.cpp:18-41, bilateralfilter_cpu.cpp:20-124; the reference's device form exists
+ * only as CUDA, bilateralfilter_cuda.cu) under monai.networks.layers.filtering.BilateralFilter.  Per output voxel out_c = sum_t w_t x_c[nb_t] / sum_t w_t with
+ * w_t = prod_axes exp(-d^2 / (2 spatial_sigma^2)) * exp(-sum_c (x_c[home] - x_c[nb_t])^2 / (2 color_sigma^2)): the colour distance is joint over the C channels,
+ * the window has K = (int)ceil(5.0f * spatial_sigma) | 1 taps (the product in float32) on every axis of extent > 1, neighbour indices are clamped to the volume.
+ * Images with fewer than three axes pass leading 1s (an axis of extent 1 has one tap: its K clamped taps would scale numerator and denominator alike).  A
+ * window that holds NaN or +-inf gives NaN as in the reference.  One launch, no workspace, no atomics, the same bits on every run; offsets are 64-bit.
+ * MH_ERR_ARG (nothing is launched): null pointers, sizes below 1, src == dst, C > 16, K > 255 (spatial_sigma > 51.0), sigmas that are not finite and positive.
+ * MH_ERR_UNSUPPORTED: B > 65535 or more than 2^31 - 1 workgroups per image.
+ * mh_bilateral_window: K of a spatial sigma by the float32 rule (-1 for a sigma that is not finite and positive).  Host arithmetic only.
+ * mh_bilateral_filter_accepts: host arithmetic only -- 0: not supported, 1: the LDS tile kernel (float32, C <= 4, the tile of all channels with its halo within
+ * 63 KiB), 2: the generic kernel (taps from global memory; float64, C > 4, larger windows).  A colour sigma whose scale sqrt(log2(e) / (2 color_sigma^2)) or
+ * its inverse is not a normal float32 runs on the generic kernel whatever this returns. */
+int mh_bilateral_window(float spatial_sigma);
+int mh_bilateral_filter_accepts(int C, int D, int H, int W, int K, int is_f64);
+int mh_bilateral_filter_f32(const float* src, float* dst, int B, int C, int D, int H, int W, float spatial_sigma, float color_sigma, void* stream);
+int mh_bilateral_filter_f64(const double* src, double* dst, int B, int C, int D, int H, int W, float spatial_sigma, float color_sigma, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """Stand-in for the reference's native module ``monai._C`` (pybind11, monai/csrc/ext.cpp:20-80) on the MI355X kernels.
 
-Exports the resampling surface of that module -- ``grid_pull`` / ``grid_push`` / ``grid_count`` / ``grid_grad`` and their
+Exports the exact bilateral filter ``bilateral_filter(input, spatial_sigma, color_sigma, fast_approx=False)`` (ext.cpp:23; the reference's device form
+is CUDA only) -- ``fast_approx=True``, the permutohedral-lattice approximation, is not built and raises ``RuntimeError`` -- and the resampling surface of that module -- ``grid_pull`` / ``grid_push`` / ``grid_count`` / ``grid_grad`` and their
 ``*_backward`` functions (ext.cpp:67-74, interpolation orders 0-7, every index-remapping boundary condition) -- and
 the ``BoundType`` / ``InterpolationType`` enums with ``__members__`` lookup including the aliases (used at
 monai/networks/layers/spatial_transforms.py:123-127).  The "sliding" boundary condition (unfinished in the reference,
@@ -19,7 +20,7 @@ from . import _lib
 
 __all__ = [
     "BoundType", "InterpolationType", "grid_pull", "grid_pull_backward", "grid_push", "grid_push_backward", "grid_count",
-    "grid_count_backward", "grid_grad", "grid_grad_backward",
+    "grid_count_backward", "grid_grad", "grid_grad_backward", "bilateral_filter",
 ]
 
 
@@ -191,3 +192,14 @@ def grid_grad_backward(grad, input, grid, bound, interpolation, extrapolate):
     """``monai._C.grid_grad_backward`` (pushpull.h:469-507); grad is (B, C, spatial of grid, D)."""
     return _pushpull("grid_grad_backward", input, None, grid, grad, bound, interpolation, extrapolate,
                      do_push=input.requires_grad, do_grad=grid.requires_grad)
+
+
+def bilateral_filter(input: torch.Tensor, spatial_sigma: float, color_sigma: float, fast_approx: bool) -> torch.Tensor:
+    """``monai._C.bilateral_filter`` (ext.cpp:23, filtering/bilateral/bilateral.cpp:18-41): input (B, C, X[, Y[, Z]]).  Only the exact filter is built:
+    the reference's two permutohedral implementations (``fast_approx=True``) do not agree with each other and splat with float atomics."""
+    if fast_approx:
+        raise RuntimeError("bilateral_filter: the permutohedral-lattice approximation (fast_approx=True) is not built; pass fast_approx=False "
+                           "for the exact filter")
+    from . import ops
+
+    return ops.bilateral_filter(input, spatial_sigma, color_sigma)

@@ -147,6 +147,10 @@ SIGNATURES = {
     "mh_separable_filter3d_f32": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _I, C.POINTER(C.c_float), _I, C.POINTER(C.c_float), _I, _P]),
     "mh_median_filter_accepts": (_I, [_I, _I, _I, _I, _I, _I]),
     "mh_median_filter_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mh_bilateral_window": (_I, [_F]),
+    "mh_bilateral_filter_accepts": (_I, [_I, _I, _I, _I, _I, _I]),
+    "mh_bilateral_filter_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P]),
+    "mh_bilateral_filter_f64": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P]),
     "mh_spline_workspace_bytes": (_L, [_I] * 7),
     "mh_spline_prefilter_f64": (_I, [_P, _P] + [_I] * 7 + [_P]),
     "mh_spline_resample_affine_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(C.c_double), _I, _I, _P]),

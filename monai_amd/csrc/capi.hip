@@ -29,6 +29,7 @@
 #include "kernels/preproc.h"
 #include "kernels/select.h"
 #include "kernels/median.h"
+#include "kernels/bilateral.h"
 #include "kernels/spline.h"
 #include "kernels/nn_simple.h"
 #include "kernels/conv1x1_h2.h"
@@ -2332,6 +2333,126 @@ int mh_spline_resample_grid_f32(const void* vol, int NC, int rank, int Di, int H
     }
     if (coords_f64) return spline_launch<true, double>(vol, static_cast<const double*>(coords), dst, a, (hipStream_t)stream);
     return spline_launch<true, float>(vol, static_cast<const float*>(coords), dst, a, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------ bilateral filter (bilateral.h)
+struct BilateralPlan { int path; int hz, hy, hx, la, lb, pitch, py, pz, lds; long long tiles_x, tiles_y, tiles_z; };
+
+// the reference's window: (int)ceil(5.0f * sigma) | 1 with the product in float32 (bilateralfilter_cpu.cpp:30); -1 for a sigma that is not finite and positive
+static int bilateral_window(float sigma) {
+    if (!(sigma > 0.0f) || !(sigma <= 3.4028234e38f)) return -1;
+    volatile float p = 5.0f * sigma;      // volatile: rounded to float32 whatever the host's evaluation method
+    if (!(p < 2147483000.0f)) return 0x7fffffff;
+    return (int)ceilf(p) | 1;
+}
+
+// 0: not supported (why: *why), 1: bilateral_tile_kernel, 2: bilateral_generic_kernel.  Host arithmetic only.  The tile path: float32, C <= 4, lanes 2^a x 2^b x
+// 2^(8-a-b) with 4 outputs along x each (one lane along an axis of extent 1); of the boxes whose staged tile (all channels, halo, row pitch) fits, the one with
+// the smallest tile (ties: the longest rows), among those that fit 16 KiB if there is one, else among those that fit 63 KiB.  The box depends on the window, the
+// channel count and on which axes have extent 1, not on the image size.
+static int bilateral_plan(int C, int D, int H, int W, int K, int is_f64, BilateralPlan& p, const char** why) {
+    p.path = 0;
+    if (C < 1 || D < 1 || H < 1 || W < 1) { *why = "sizes must be positive"; return 0; }
+    if (C > BIL_MAX_C) { *why = "Bilateral filtering not implemented for channel count > 16"; return 0; }
+    if (K < 1 || !(K & 1)) { *why = "the window must be odd and positive"; return 0; }
+    if (K > BIL_MAX_K) { *why = "windows of more than 255 taps per axis are not supported"; return 0; }
+    const int h = K / 2;
+    p.hz = D > 1 ? h : 0; p.hy = H > 1 ? h : 0; p.hx = W > 1 ? h : 0;
+    p.la = p.lb = p.pitch = p.py = p.pz = p.lds = 0;
+    p.tiles_x = p.tiles_y = p.tiles_z = 0;
+    if (!is_f64 && C <= BIL_TILE_MAX_C && (p.hz | p.hy | p.hx)) {      // a window of one tap returns its input bit for bit: not through the scaling of the tile path
+        for (int cls = 0; cls < 2 && !p.path; ++cls) {
+            const long long cap = cls ? BIL_LDS_LARGE : BIL_LDS_SMALL;
+            long long best = -1;
+            for (int a = 8; a >= 0; --a)
+                for (int b = 8 - a; b >= 0; --b) {
+                    const long long tx = (long long)BIL_R << a, ty = 1LL << b, tz = 256 >> (a + b);
+                    if ((H == 1 && b) || (D == 1 && a + b != 8) || (W == 1 && a && !(D == 1 && H == 1))) continue;
+                    const long long pitch = (tx + 2 * p.hx + 4) / 4 * 4, py = ty + 2 * p.hy, pz = tz + 2 * p.hz, vol = C * pitch * py * pz;      // a row is read one float past its staged columns
+                    if (vol > cap) continue;
+                    const long long nx = (W + tx - 1) / tx, ny = (H + ty - 1) / ty, nz = (D + tz - 1) / tz;
+                    if (nx * ny > 0x7fffffffLL || nx * ny * nz > 0x7fffffffLL) continue;
+                    if (best < 0 || vol < best) {
+                        best = vol; p.path = 1; p.la = a; p.lb = b; p.pitch = (int)pitch; p.py = (int)py; p.pz = (int)pz; p.lds = cls;
+                        p.tiles_x = nx; p.tiles_y = ny; p.tiles_z = nz;
+                    }
+                }
+        }
+        if (p.path) return 1;
+    }
+    if ((double)D * H * W > 256.0 * 0x7fffffff) { *why = "more than 2^31 - 1 workgroups per image"; return 0; }
+    const long long blocks = ((long long)D * H * W + 255) / 256;
+    p.tiles_x = blocks; p.tiles_y = p.tiles_z = 1;
+    p.path = 2;
+    return 2;
+}
+
+int mh_bilateral_window(float spatial_sigma) { return bilateral_window(spatial_sigma); }
+
+int mh_bilateral_filter_accepts(int C, int D, int H, int W, int K, int is_f64) {
+    BilateralPlan p;
+    const char* why = "";
+    return bilateral_plan(C, D, H, W, K, is_f64, p, &why);
+}
+
+template <int C>
+static void bilateral_tile_launch(const float* src, float* dst, const BilTile& g, int large, dim3 grid, hipStream_t stream) {
+    if (large) hipLaunchKernelGGL((bilateral_tile_kernel<C, BIL_LDS_LARGE>), grid, dim3(256), 0, stream, src, dst, g);
+    else hipLaunchKernelGGL((bilateral_tile_kernel<C, BIL_LDS_SMALL>), grid, dim3(256), 0, stream, src, dst, g);
+}
+
+template <typename T>
+static int bilateral_filter(const T* src, T* dst, int B, int C, int D, int H, int W, float spatial_sigma, float color_sigma, void* stream) {
+    const int is_f64 = sizeof(T) == 8;
+    if (!src || !dst) return fail(MH_ERR_ARG, "bilateral_filter: null pointer");
+    if (B < 1 || C < 1 || D < 1 || H < 1 || W < 1) return fail(MH_ERR_ARG, "bilateral_filter: sizes must be positive (B %d, C %d, volume %d x %d x %d)", B, C, D, H, W);
+    if (src == dst) return fail(MH_ERR_ARG, "bilateral_filter: src and dst must not be the same buffer (every output reads its neighbours' inputs)");
+    if (C > BIL_MAX_C) return fail(MH_ERR_ARG, "bilateral_filter: Bilateral filtering not implemented for channel count > 16 (C = %d)", C);
+    const int K = bilateral_window(spatial_sigma);
+    if (K < 0 || bilateral_window(color_sigma) < 0)
+        return fail(MH_ERR_ARG, "bilateral_filter: sigmas must be finite and positive (spatial %g, color %g)", (double)spatial_sigma, (double)color_sigma);
+    if (K > BIL_MAX_K) return fail(MH_ERR_ARG, "bilateral_filter: a window of K = %d taps per axis (spatial sigma %g) is above the limit of 255 (sigma <= 51.0)", K, (double)spatial_sigma);
+    BilateralPlan p;
+    const char* why = "";
+    if (!bilateral_plan(C, D, H, W, K, is_f64, p, &why)) return fail(MH_ERR_UNSUPPORTED, "bilateral_filter: %s (volume %d x %d x %d, K = %d)", why, D, H, W, K);
+    if (B > 65535) return fail(MH_ERR_UNSUPPORTED, "bilateral_filter: more than 65535 batch items per call (B = %d)", B);
+    // the reference's constants are float32: -1.0f / (2 * sigma * sigma), converted to the tensor's type afterwards (bilateralfilter_cpu.cpp:32-33)
+    const float ks = 1.0f / (2 * spatial_sigma * spatial_sigma), kc = 1.0f / (2 * color_sigma * color_sigma);
+    const double log2e = 1.4426950408889634;
+    const float s = (float)sqrt((double)kc * log2e), inv_s = 1.0f / s;
+    const bool scalable = s >= 1.17549435e-38f && s <= 3.4028234e38f && inv_s >= 1.17549435e-38f && inv_s <= 3.4028234e38f && kc <= 3.4028234e38f;
+    if (p.path == 1 && !scalable) {      // the pre-scaled values would leave float32's range: the reference's formulation
+        p.path = 2;
+        p.tiles_x = ((long long)D * H * W + 255) / 256;
+        p.tiles_y = p.tiles_z = 1;
+    }
+    const dim3 grid((unsigned)(p.tiles_x * p.tiles_y * p.tiles_z), (unsigned)B);
+    if (p.path == 1) {
+        if constexpr (sizeof(T) == 4) {
+            BilTile g;
+            g.D = D; g.H = H; g.W = W; g.K = K; g.hz = p.hz; g.hy = p.hy; g.hx = p.hx; g.la = p.la; g.lb = p.lb; g.pitch = p.pitch; g.py = p.py; g.pz = p.pz;
+            g.tiles_x = (int)p.tiles_x; g.tiles_y = (int)p.tiles_y; g.vec = W % 4 == 0 && aligned(dst, 16);
+            g.ks = (float)((double)ks * log2e); g.s = s; g.inv_s = inv_s;
+            switch (C) {
+                case 1: bilateral_tile_launch<1>(src, dst, g, p.lds, grid, (hipStream_t)stream); break;
+                case 2: bilateral_tile_launch<2>(src, dst, g, p.lds, grid, (hipStream_t)stream); break;
+                case 3: bilateral_tile_launch<3>(src, dst, g, p.lds, grid, (hipStream_t)stream); break;
+                default: bilateral_tile_launch<4>(src, dst, g, p.lds, grid, (hipStream_t)stream); break;
+            }
+        }
+    } else {
+        BilGeneric<T> g;
+        g.C = C; g.D = D; g.H = H; g.W = W; g.hz = p.hz; g.hy = p.hy; g.hx = p.hx; g.ks = (T)ks; g.kc = (T)kc;
+        hipLaunchKernelGGL(bilateral_generic_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, g);
+    }
+    return launched("bilateral_filter");
+}
+
+int mh_bilateral_filter_f32(const float* src, float* dst, int B, int C, int D, int H, int W, float spatial_sigma, float color_sigma, void* stream) {
+    return bilateral_filter<float>(src, dst, B, C, D, H, W, spatial_sigma, color_sigma, stream);
+}
+int mh_bilateral_filter_f64(const double* src, double* dst, int B, int C, int D, int H, int W, float spatial_sigma, float color_sigma, void* stream) {
+    return bilateral_filter<double>(src, dst, B, C, D, H, W, spatial_sigma, color_sigma, stream);
 }
 
 // ------------------------------------------------------------------------------------------ Gaussian smoothing

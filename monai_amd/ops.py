@@ -750,6 +750,56 @@ def spline_resample(x: torch.Tensor, order: int, mode: str, out_size: Sequence[i
     return out
 
 
+BILATERAL_MAX_WINDOW = 255      # BIL_MAX_K of csrc/kernels/bilateral.h: taps per axis (spatial sigma <= 51.0)
+BILATERAL_MAX_CHANNELS = 16     # the limit of the reference's device build (filtering/bilateral/bilateral.cpp:29-32)
+
+
+def bilateral_window(spatial_sigma: float) -> int:
+    """Taps per axis of the exact bilateral filter: ``(int)ceil(5.0f * spatial_sigma) | 1`` with the product in float32, as the reference evaluates it
+    (bilateralfilter_cpu.cpp:30): 0.2 -> 1, 0.6 -> 3, 1 -> 5, 2.2 -> 11, 51.0 -> 255.  Host arithmetic; -1 for a sigma that is not finite and positive."""
+    return int(_lib.lib()._mh_bilateral_window(float(spatial_sigma)))
+
+
+def bilateral_filter_path(spatial_shape: Sequence[int], channels: int, spatial_sigma: float, dtype=torch.float32) -> int:
+    """Which kernel serves the exact bilateral filter on images of ``spatial_shape`` (1 to 3 axes) with ``channels`` channels: 0 none, 1 the LDS tile kernel
+    (float32, at most 4 channels, the tile with its halo within 63 KiB), 2 the generic kernel (taps from global memory).  Host arithmetic."""
+    dims = (1,) * (3 - len(spatial_shape)) + tuple(int(v) for v in spatial_shape)
+    k = bilateral_window(spatial_sigma)
+    if k < 1:
+        return 0
+    return _lib.lib().query("mh_bilateral_filter_accepts", int(channels), *dims, k, int(dtype == torch.float64))
+
+
+def bilateral_filter(x: torch.Tensor, spatial_sigma: float, color_sigma: float) -> torch.Tensor:
+    """The exact bilateral filter of ``x`` (B, C, 1 to 3 spatial axes) -- ``monai._C.bilateral_filter(x, spatial_sigma, color_sigma, False)``
+    (monai/csrc/filtering/bilateral/bilateralfilter_cpu.cpp:20-124) as one kernel launch: a Gaussian of ``spatial_sigma`` over a window of
+    ``ceil(5 spatial_sigma) | 1`` taps per axis with clamped indices, times a Gaussian of ``color_sigma`` over the colour distance taken jointly over the
+    channels.  float32 and float64 run natively; float16 is evaluated in float32 and rounded once.  A window that holds NaN or inf gives NaN, as there.
+    No host synchronisation."""
+    if x.dim() < 3 or x.dim() > 5:
+        raise RuntimeError("Bilateral filtering not implemented for spatial dimension > 3." if x.dim() > 5 else
+                           f"monai_amd.bilateral_filter: (B, C, 1 to 3 spatial axes) required, got shape {tuple(x.shape)}")
+    if x.dtype == torch.float16:
+        return bilateral_filter(x.float(), spatial_sigma, color_sigma).half()
+    _lib.require_device(x, dtypes=(torch.float32, torch.float64))
+    if int(x.shape[1]) > BILATERAL_MAX_CHANNELS:
+        raise RuntimeError("Bilateral filtering not implemented for channel count > 16.")
+    k = bilateral_window(spatial_sigma)
+    if k > BILATERAL_MAX_WINDOW:
+        raise RuntimeError(f"monai_amd.bilateral_filter: spatial_sigma {spatial_sigma} gives a window of K = {k} taps per axis; at most {BILATERAL_MAX_WINDOW} (sigma <= 51.0)")
+    src = x.contiguous()
+    out = torch.empty_like(src)
+    if not src.numel():
+        return out
+    dims = (1,) * (5 - src.dim()) + tuple(int(v) for v in src.shape[2:])
+    name = "mh_bilateral_filter_f64" if src.dtype == torch.float64 else "mh_bilateral_filter_f32"
+    try:
+        _lib.lib().call(name, _lib.ptr(src), _lib.ptr(out), int(src.shape[0]), int(src.shape[1]), *dims, float(spatial_sigma), float(color_sigma), _s(x))
+    except _lib.KernelRejected as e:
+        raise _lib.UnsupportedOnDevice(str(e)) from None
+    return out
+
+
 def add_act(a, a_nrm, b, b_nrm, slope: float, out, out_nrm=None):
     """out = leaky_relu(act(a) + act(b), slope) -- residual join of UnetResBlock.  out_nrm: `nrm_identity` records of `out` (magnitude bound)."""
     _lib.require_device(a, a_nrm, b, b_nrm, out, out_nrm)

@@ -122,6 +122,7 @@ _TARGETS = {
         "grid_grad": ("monai_amd.networks.layers.spatial_transforms", "grid_grad"),
     },
     "monai.networks.layers.simplelayers": {n: ("monai_amd.networks.layers.simplelayers", n) for n in ("GaussianFilter", "MedianFilter", "median_filter")},
+    "monai.networks.layers.filtering": {"BilateralFilter": ("monai_amd.networks.layers.filtering", "BilateralFilter")},
     "monai.networks.blocks.warp": {"Warp": ("monai_amd.networks.blocks.warp", "Warp"), "DVF2DDF": ("monai_amd.networks.blocks.warp", "DVF2DDF")},
     "monai.metrics.meandice": {n: ("monai_amd.metrics.meandice", n) for n in ("DiceMetric", "compute_dice", "DiceHelper")},
     "monai.metrics.meaniou": {n: ("monai_amd.metrics.meaniou", n) for n in ("MeanIoU", "compute_iou")},
