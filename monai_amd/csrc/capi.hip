@@ -7,6 +7,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "kernels/common.h"
 #include "kernels/attention.h"
 #include "kernels/conv3d_mfma.h"
@@ -56,6 +58,30 @@ static int launched(const char* what) {
     return MH_OK;
 }
 static inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
+static inline bool too_large_for(long long n) { return n > 0x7fffffffLL * 256; }      // blocks_for(n) would pass the grid's x limit
+
+// Run-time value -> template argument.  Each helper hands compile-time constants to a generic lambda, which names its kernel
+// template once: `kernel<KT, ST>` with the lambda's own parameters, which convert to int / bool as constant expressions.  The
+// lambda either launches, or stores the instantiation's address where an occupancy query and the launch must agree on it.
+// with_flags(f, a, b, ...): f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...) -- 2^n instantiations; a form that exists
+// for fewer keeps its fixed arguments literal.
+template <class F> static inline void with_flags(F&& f) { f(); }
+template <class F, class... B> static inline void with_flags(F&& f, bool b0, B... rest) {
+    if (b0) with_flags([&](auto... bs) { f(std::true_type{}, bs...); }, rest...);
+    else with_flags([&](auto... bs) { f(std::false_type{}, bs...); }, rest...);
+}
+// with_int<V0, V1, ...>(v, f): f(std::integral_constant<int, Vi>{}) for the Vi that equals v; false (f not called) when none does
+template <int... Vs, class F> static inline bool with_int(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+template <int V> constexpr std::integral_constant<int, V> int_c{};      // a value that is fixed on one path of a lambda fed by with_int
+// with_type<T0, T1, ...>(i, f): f(type_tag<Ti>{}) for a dtype / precision code i in 0 .. n-1; false when i is outside
+template <class T> struct type_tag { using type = T; };
+template <class... Ts, class F> static inline bool with_type(int i, F&& f) {
+    int k = 0;
+    return ((i == k++ ? (f(type_tag<Ts>{}), true) : false) || ...);
+}
+#define MH_TYPE(TAG) typename decltype(TAG)::type
 static inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 static inline bool fits_i32(long long n) { return n < 2147483647LL; }
 static bool dense_ok(const mh_tensor5* t) {
@@ -123,41 +149,22 @@ int mh_window_extract_f32(const float* vol, int C, int D, int H, int W, const in
         return fail(MH_ERR_ARG, "window_extract: window leaves the volume");
     const bool v4 = rw % 4 == 0 && W % 4 == 0 && all_mult4(sx, nx) && aligned(vol, 16) && aligned(out, 16);
     const long long total = (long long)nwin * C * rd * rh * (v4 ? rw / 4 : rw);
-    if (total > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "window_extract: problem too large for one launch");
+    if (too_large_for(total)) return fail(MH_ERR_UNSUPPORTED, "window_extract: problem too large for one launch");
     RegGrid rg;
     if (regular_grid(rg, sz, nz, sy, ny, sx, nx, D, H, W)) {      // dense_patch_slices: closed-form starts, any number of windows per axis
-        if (v4)
-            hipLaunchKernelGGL((window_extract_reg_kernel<4>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, vol, C, D, H, W, rg,
+        with_int<1, 4>(v4 ? 4 : 1, [&](auto VEC) {
+            hipLaunchKernelGGL((window_extract_reg_kernel<VEC>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, vol, C, D, H, W, rg,
                                w0, nwin, rd, rh, rw, out);
-        else
-            hipLaunchKernelGGL((window_extract_reg_kernel<1>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, vol, C, D, H, W, rg,
-                               w0, nwin, rd, rh, rw, out);
+        });
         return launched("window_extract");
     }
     WindowGrid g;
     if (int e = fill_grid(g, sz, nz, sy, ny, sx, nx)) return e;
-    if (v4)
-        hipLaunchKernelGGL((window_extract_kernel<4>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, vol, C, D,
+    with_int<1, 4>(v4 ? 4 : 1, [&](auto VEC) {
+        hipLaunchKernelGGL((window_extract_kernel<VEC>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, vol, C, D,
                            H, W, g, w0, nwin, rd, rh, rw, out);
-    else
-        hipLaunchKernelGGL((window_extract_kernel<1>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, vol, C, D,
-                           H, W, g, w0, nwin, rd, rh, rw, out);
+    });
     return launched("window_extract");
-}
-
-template <int VEC>
-static void launch_blend(int kt, unsigned nb, hipStream_t s, const float* logits, const float* imp, float* out, int K, int k0,
-                         int D, int H, int W, int rd, int rh, int rw, const WindowGrid& g, int premul, long long wstride) {
-#define MH_BLEND_CASE(KT)                                                                                              \
-    case KT:                                                                                                           \
-        hipLaunchKernelGGL((sw_blend_kernel<KT, VEC>), dim3(nb), dim3(256), 0, s, logits, imp, out, K, k0, D, H, W, rd, \
-                           rh, rw, g, premul, wstride);                                                                \
-        break;
-    switch (kt) {
-        MH_BLEND_CASE(1) MH_BLEND_CASE(2) MH_BLEND_CASE(3) MH_BLEND_CASE(4)
-        MH_BLEND_CASE(5) MH_BLEND_CASE(6) MH_BLEND_CASE(7) MH_BLEND_CASE(8)
-    }
-#undef MH_BLEND_CASE
 }
 
 int mh_patch_accumulate_f32(float* values, uint8_t* counts, const float* patch, int NC, int D, int H, int W, int pd, int ph, int pw,
@@ -167,7 +174,7 @@ int mh_patch_accumulate_f32(float* values, uint8_t* counts, const float* patch, 
     if (z0 < 0 || y0 < 0 || x0 < 0 || z0 + pd > D || y0 + ph > H || x0 + pw > W)
         return fail(MH_ERR_ARG, "patch_accumulate: the patch (%d,%d,%d)+(%d,%d,%d) leaves the merged volume (%d,%d,%d)", z0, y0, x0, pd, ph, pw, D, H, W);
     const long long total = (long long)NC * pd * ph * pw;
-    if (total > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "patch_accumulate: problem too large for one launch");
+    if (too_large_for(total)) return fail(MH_ERR_UNSUPPORTED, "patch_accumulate: problem too large for one launch");
     hipLaunchKernelGGL(patch_accumulate_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, values, counts, patch, NC, D, H, W, pd, ph, pw, z0, y0, x0);
     return launched("patch_accumulate");
 }
@@ -189,7 +196,7 @@ int mh_patch_accumulate_batch_f32(float* values, uint8_t* counts, const float* p
             for (int a = 0; a < 3; ++a) { lo[a] = l[a] < lo[a] ? l[a] : lo[a]; hi[a] = e[a] > hi[a] ? e[a] : hi[a]; }
         }
         const long long total = (long long)NC * (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
-        if (total > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "patch_accumulate_batch: problem too large for one launch");
+        if (too_large_for(total)) return fail(MH_ERR_UNSUPPORTED, "patch_accumulate_batch: problem too large for one launch");
         hipLaunchKernelGGL(patch_accumulate_batch_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, values, counts,
                            patches + (long long)p0 * NC * pd * ph * pw, NC, D, H, W, pd, ph, pw, b, lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]);
     }
@@ -198,7 +205,7 @@ int mh_patch_accumulate_batch_f32(float* values, uint8_t* counts, const float* p
 
 int mh_avg_finalize_f32(float* values, const uint8_t* counts, int64_t n, void* stream) {
     if (!values || !counts || n < 1) return fail(MH_ERR_ARG, "avg_finalize: bad argument");
-    if (n > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "avg_finalize: problem too large for one launch");
+    if (too_large_for(n)) return fail(MH_ERR_UNSUPPORTED, "avg_finalize: problem too large for one launch");
     hipLaunchKernelGGL(avg_finalize_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, values, counts, (long long)n);
     return launched("avg_finalize");
 }
@@ -208,32 +215,19 @@ int mh_avg_finalize_f32(float* values, const uint8_t* counts, int64_t n, void* s
 template <bool ARGMAX>
 static int launch_blend_reg(int kt, bool v4, int G, bool nt, unsigned nb, hipStream_t s, const float* logits, const float* imp, void* out,
                             int K, int k0, int D, int H, int W, int rd, int rh, int rw, const RegGrid& g, int premul, int out_u8, long long wstride) {
-#define MH_BR(KT, VEC, GG, NTT)                                                                                              \
-    hipLaunchKernelGGL((sw_blend_reg_kernel<KT, VEC, GG, NTT, ARGMAX>), dim3(nb), dim3(256), 0, s, logits, imp, out, K, k0, D, H, \
-                       W, rd, rh, rw, g, premul, out_u8, wstride)
-#define MH_BR_CASE(KT)                                                                      \
-    case KT:                                                                                \
-        if (!v4) MH_BR(KT, 1, 1, false);                                                    \
-        else if (nt) MH_BR(KT, 4, MH_BLEND_G, true);                                        \
-        else MH_BR(KT, 4, MH_BLEND_G, false);                                               \
-        break;
+    // the one launch line: KT, VEC, GG, NT are integral constants
+    auto launch = [&](auto KT, auto VEC, auto GG, auto NT) {
+        hipLaunchKernelGGL((sw_blend_reg_kernel<KT, VEC, GG, NT, ARGMAX>), dim3(nb), dim3(256), 0, s, logits, imp, out, K, k0, D, H,
+                           W, rd, rh, rw, g, premul, out_u8, wstride);
+    };
     if (v4 && kt == 5 && !ARGMAX && G != MH_BLEND_G) {       // the benchmark shape carries every batch size
-        switch (G) {
-            case 1: if (nt) MH_BR(5, 4, 1, true); else MH_BR(5, 4, 1, false); return MH_OK;
-            case 2: if (nt) MH_BR(5, 4, 2, true); else MH_BR(5, 4, 2, false); return MH_OK;
-            case 4: if (nt) MH_BR(5, 4, 4, true); else MH_BR(5, 4, 4, false); return MH_OK;
-            case 8: if (nt) MH_BR(5, 4, 8, true); else MH_BR(5, 4, 8, false); return MH_OK;
-            default: break;
-        }
+        if (with_int<1, 2, 4, 8>(G, [&](auto GG) { with_flags([&](auto NT) { launch(int_c<5>, int_c<4>, GG, NT); }, nt); })) return MH_OK;
     }
-    switch (kt) {
-        MH_BR_CASE(1) MH_BR_CASE(2) MH_BR_CASE(3) MH_BR_CASE(4)
-        MH_BR_CASE(5) MH_BR_CASE(6) MH_BR_CASE(7) MH_BR_CASE(8)
-        default: return fail(MH_ERR_ARG, "sw_blend: bad channel chunk %d", kt);
-    }
-#undef MH_BR_CASE
-#undef MH_BR
-    return MH_OK;
+    const bool known = with_int<1, 2, 3, 4, 5, 6, 7, 8>(kt, [&](auto KT) {
+        if (!v4) launch(KT, int_c<1>, int_c<1>, std::false_type{});       // the non-vector path: no batching, no non-temporal accesses
+        else with_flags([&](auto NT) { launch(KT, int_c<4>, int_c<MH_BLEND_G>, NT); }, nt);
+    });
+    return known ? MH_OK : fail(MH_ERR_ARG, "sw_blend: bad channel chunk %d", kt);
 }
 
 static int blend_checks(const char* what, const float* logits, const float* imp, const void* out, int K, int D, int H, int W, int rd, int rh, int rw,
@@ -253,7 +247,7 @@ static int blend_checks(const char* what, const float* logits, const float* imp,
             if (ss[a][i] > ss[a][i - 1] + rr[a]) return fail(MH_ERR_ARG, "%s: uncovered gap on axis %d", what, a);
         }
     }
-    if ((long long)D * H * W > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "%s: problem too large for one launch", what);
+    if (too_large_for((long long)D * H * W)) return fail(MH_ERR_UNSUPPORTED, "%s: problem too large for one launch", what);
     return MH_OK;
 }
 
@@ -278,8 +272,12 @@ int mh_sw_blend_f32(const float* logits, int64_t window_stride, const float* imp
     if (int e = fill_grid(g, sz, nz, sy, ny, sx, nx)) return e;
     for (int k0 = 0; k0 < K; k0 += 8) {
         const int kt = K - k0 < 8 ? K - k0 : 8;
-        if (v4) launch_blend<4>(kt, blocks_for(total), (hipStream_t)stream, logits, imp, out, K, k0, D, H, W, rd, rh, rw, g, premultiplied ? 1 : 0, window_stride);
-        else launch_blend<1>(kt, blocks_for(total), (hipStream_t)stream, logits, imp, out, K, k0, D, H, W, rd, rh, rw, g, premultiplied ? 1 : 0, window_stride);
+        with_int<1, 4>(v4 ? 4 : 1, [&](auto VEC) {
+            with_int<1, 2, 3, 4, 5, 6, 7, 8>(kt, [&](auto KT) {
+                hipLaunchKernelGGL((sw_blend_kernel<KT, VEC>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, logits, imp, out, K, k0, D, H, W, rd,
+                                   rh, rw, g, premultiplied ? 1 : 0, (long long)window_stride);
+            });
+        });
     }
     return launched("sw_blend");
 }
@@ -296,14 +294,14 @@ int mh_sw_blend_buffered_f32(const float* logits, int64_t window_stride, const f
     hipStream_t s = (hipStream_t)stream;
     for (int k0 = 0; k0 < K; k0 += 4) {
         const int kt = K - k0 < 4 ? K - k0 : 4;
-#define MH_BB(KT_, V_)                                                                                                                                          \
-    {                                                                                                                                                          \
-        if (premultiplied) hipLaunchKernelGGL((sw_blend_buffered_kernel<KT_, V_, true>), dim3(blocks_for(total)), dim3(256), 0, s, logits, imp, out, K, k0, D, H, W, rd, rh, rw, g, buffer_axis, buffer_steps, (long long)window_stride); \
-        else hipLaunchKernelGGL((sw_blend_buffered_kernel<KT_, V_, false>), dim3(blocks_for(total)), dim3(256), 0, s, logits, imp, out, K, k0, D, H, W, rd, rh, rw, g, buffer_axis, buffer_steps, (long long)window_stride);           \
-    }
-        if (v4) { if (kt == 4) MH_BB(4, 4) else if (kt == 3) MH_BB(3, 4) else if (kt == 2) MH_BB(2, 4) else MH_BB(1, 4) }
-        else { if (kt == 4) MH_BB(4, 1) else if (kt == 3) MH_BB(3, 1) else if (kt == 2) MH_BB(2, 1) else MH_BB(1, 1) }
-#undef MH_BB
+        with_int<1, 2, 3, 4>(kt, [&](auto KT) {
+            with_int<1, 4>(v4 ? 4 : 1, [&](auto VEC) {
+                with_flags([&](auto PREMUL) {
+                    hipLaunchKernelGGL((sw_blend_buffered_kernel<KT, VEC, PREMUL>), dim3(blocks_for(total)), dim3(256), 0, s, logits, imp, out, K, k0, D, H, W, rd, rh, rw, g,
+                                       buffer_axis, buffer_steps, (long long)window_stride);
+                }, premultiplied != 0);
+            });
+        });
     }
     return launched("sw_blend_buffered");
 }
@@ -359,22 +357,20 @@ int mh_sw_blend_mosaic_f32(const float* logits, const int64_t* class_base, int l
             }
         }
     const bool fast = max_cs * K < MH_BLEND_IDX32_LIMIT && max_zy < (1LL << 24) && max_ext < (1LL << 23) && std::max(D, std::max(H, W)) < (1 << 23) && knob_int("MONAI_AMD_BLEND_IDX64", 0) == 0;
-#define MH_BM(KT, G_, NT_, SEP_) { if (fast) hipLaunchKernelGGL((sw_blend_mosaic_kernel<KT, G_, NT_, SEP_, true>), dim3(nb, D), dim3(256), 0, s, logits, imp, out, K, D, H, W, rd, rh, rw, rg, ms); \
-                                   else hipLaunchKernelGGL((sw_blend_mosaic_kernel<KT, G_, NT_, SEP_, false>), dim3(nb, D), dim3(256), 0, s, logits, imp, out, K, D, H, W, rd, rh, rw, rg, ms); }
+    auto launch = [&](auto KT, auto GG, auto NT, auto SEP) {
+        with_flags([&](auto FAST) {
+            hipLaunchKernelGGL((sw_blend_mosaic_kernel<KT, GG, NT, SEP, FAST>), dim3(nb, D), dim3(256), 0, s, logits, imp, out, K, D, H, W, rd, rh, rw, rg, ms);
+        }, fast);
+    };
 #ifdef MH_DEV_KNOBS
     if (K == 5 && !imp_factored) {        // A/B of the window-batch size and of non-temporal accesses on the benchmark shape (tools/blend_bench.py with the -DMH_DEV_KNOBS library)
         const int g_ = knob_int("MONAI_AMD_BLEND_G", MH_BLEND_G), nt_ = knob_int("MONAI_AMD_BLEND_NT", 0);
-        if (g_ == 1 && !nt_) { MH_BM(5, 1, false, false) return launched("sw_blend_mosaic"); }
-        if (g_ == 1 && nt_) { MH_BM(5, 1, true, false) return launched("sw_blend_mosaic"); }
-        if (g_ == 2 && nt_) { MH_BM(5, 2, true, false) return launched("sw_blend_mosaic"); }
-        if (g_ == 4 && !nt_) { MH_BM(5, 4, false, false) return launched("sw_blend_mosaic"); }
-        if (g_ == 4 && nt_) { MH_BM(5, 4, true, false) return launched("sw_blend_mosaic"); }
+        if (g_ == 2 && !nt_) {}       // the product's form, below
+        else if (with_int<1, 2, 4>(g_, [&](auto GG) { with_flags([&](auto NT) { launch(int_c<5>, GG, NT, std::false_type{}); }, nt_ != 0); }))
+            return launched("sw_blend_mosaic");
     }
 #endif
-#define MH_BM_CASE(KT) case KT: if (imp_factored) MH_BM(KT, MH_BLEND_G, false, true) else MH_BM(KT, MH_BLEND_G, false, false) break;
-    switch (K) { MH_BM_CASE(1) MH_BM_CASE(2) MH_BM_CASE(3) MH_BM_CASE(4) MH_BM_CASE(5) MH_BM_CASE(6) MH_BM_CASE(7) MH_BM_CASE(8) }
-#undef MH_BM_CASE
-#undef MH_BM
+    with_int<1, 2, 3, 4, 5, 6, 7, 8>(K, [&](auto KT) { with_flags([&](auto SEP) { launch(KT, int_c<MH_BLEND_G>, std::false_type{}, SEP); }, imp_factored != 0); });
     return launched("sw_blend_mosaic");
 }
 
@@ -515,6 +511,7 @@ int mh_conv3d_k3_h2v_config(void) { return MH_CFG_H2V; }
 int mh_conv3d_k3_h2w_config(void) { return MH_CFG_H2W; }
 int mh_conv3d_k3_h2w_fits(int D, int H, int W) { return hw_fits(D, H, W) ? 1 : 0; }
 
+// can mh_conv3d_k3_pool_f32 serve this layer?  the split-precision configuration's 16 x 16 regions (not the 8 x 32 shape), even extents, even z-chunks
 int mh_conv3d_k3_pool_accepts(int cfg, int Cin, int Cout, int D, int H, int W) {
     if (cfg == MH_CFG_H2W) return Cin == HWG_CIN && Cout >= HWG_CN && Cout % HWG_CN == 0 && D % 2 == 0 && hw_fits(D, H, W);
     if (cfg != MH_CFG_H2 || D < 2 || H < 2 || W < 2 || D % 2 || H % 2 || W % 4) return 0;
@@ -598,27 +595,19 @@ int mh_conv3d_k3_pack_f32(int cfg, const float* w, int Cin, int Cout, float* pac
         hipLaunchKernelGGL(conv3d_k3_wino2d_pack_kernel, dim3(blocks_for((long long)Cin * Cout)), dim3(256), 0, (hipStream_t)stream, w, Cin, Cout, packed);
         return launched("conv3d_k3_wino2d_pack");
     }
-    if (cfg == MH_CFG_H2C) {
-        if (!w || !packed || !mh_conv3d_k3_accepts(cfg, Cin, Cout)) return fail(MH_ERR_ARG, "conv3d_k3_pack: the 16-couts fp16 split kernel needs Cin %% 16 == 0, Cout %% 16 == 0");
+    if (cfg == MH_CFG_H2 || cfg == MH_CFG_H2C) {
+        const bool c16 = cfg == MH_CFG_H2C;
+        if (!w || !packed || !mh_conv3d_k3_accepts(cfg, Cin, Cout))
+            return fail(MH_ERR_ARG, c16 ? "conv3d_k3_pack: the 16-couts fp16 split kernel needs Cin %% 16 == 0, Cout %% 16 == 0"
+                                        : "conv3d_k3_pack: the fp16 split kernel needs Cin %% 16 == 0, Cout %% 16 == 0, Cout >= 32");
         const int64_t slab_floats = mh_conv3d_k3_packed_floats(cfg, Cin, Cout) - H2_TAIL;
         float* tail = packed + slab_floats;
         if (hipMemsetAsync(packed, 0, sizeof(float) * (size_t)slab_floats, (hipStream_t)stream) != hipSuccess)
             return fail(MH_ERR_LAUNCH, "conv3d_k3_pack: memset failed");
         hipLaunchKernelGGL(conv3d_k3_h2_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w, (long long)Cin * Cout * 27, tail);
-        hipLaunchKernelGGL(conv3d_k3_h2c_pack_kernel, dim3(blocks_for((long long)Cin * Cout)), dim3(256), 0, (hipStream_t)stream, w, Cin, Cout,
+        hipLaunchKernelGGL(c16 ? conv3d_k3_h2c_pack_kernel : conv3d_k3_h2_pack_kernel, dim3(blocks_for((long long)Cin * Cout)), dim3(256), 0, (hipStream_t)stream, w, Cin, Cout,
                            reinterpret_cast<_Float16*>(packed), tail);
-        return launched("conv3d_k3_h2c_pack");
-    }
-    if (cfg == MH_CFG_H2) {
-        if (!w || !packed || !mh_conv3d_k3_accepts(cfg, Cin, Cout)) return fail(MH_ERR_ARG, "conv3d_k3_pack: the fp16 split kernel needs Cin %% 16 == 0, Cout %% 16 == 0, Cout >= 32");
-        const int64_t slab_floats = mh_conv3d_k3_packed_floats(cfg, Cin, Cout) - H2_TAIL;
-        float* tail = packed + slab_floats;
-        if (hipMemsetAsync(packed, 0, sizeof(float) * (size_t)slab_floats, (hipStream_t)stream) != hipSuccess)
-            return fail(MH_ERR_LAUNCH, "conv3d_k3_pack: memset failed");
-        hipLaunchKernelGGL(conv3d_k3_h2_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w, (long long)Cin * Cout * 27, tail);
-        hipLaunchKernelGGL(conv3d_k3_h2_pack_kernel, dim3(blocks_for((long long)Cin * Cout)), dim3(256), 0, (hipStream_t)stream, w, Cin, Cout,
-                           reinterpret_cast<_Float16*>(packed), tail);
-        return launched("conv3d_k3_h2_pack");
+        return launched(c16 ? "conv3d_k3_h2c_pack" : "conv3d_k3_h2_pack");
     }
     if (cfg == MH_CFG_H2W) {
         if (!w || !packed || !mh_conv3d_k3_accepts(cfg, Cin, Cout)) return fail(MH_ERR_ARG, "conv3d_k3_pack: the Winograd split kernel needs Cin == 32, Cout %% 32 == 0");
@@ -665,17 +654,12 @@ template <class Cfg>
 static void launch_mfma(const Tensor& in, const float* wp, const float* bias, const Tensor& out, float* stats, hipStream_t s) {
     const int tx = cdiv(out.W, Cfg::TX), ty = cdiv(out.H, Cfg::TY), tz = cdiv(out.D, Cfg::TZ);
     const dim3 grid((unsigned)(tx * ty * tz), (unsigned)cdiv(out.C, Cfg::CN), (unsigned)out.N);
-    if (stats)
-        hipLaunchKernelGGL((conv3d_k3_mfma_kernel<Cfg, true>), grid, dim3(256), 0, s, in, wp, bias, out, stats, tx, ty, tz);
-    else
-        hipLaunchKernelGGL((conv3d_k3_mfma_kernel<Cfg, false>), grid, dim3(256), 0, s, in, wp, bias, out, stats, tx, ty, tz);
+    with_flags([&](auto ST) { hipLaunchKernelGGL((conv3d_k3_mfma_kernel<Cfg, ST>), grid, dim3(256), 0, s, in, wp, bias, out, stats, tx, ty, tz); }, stats != nullptr);
 }
 
 struct PoolOut { float* mx; float* mn; long long n_stride; };
 static int conv3d_k3_launch(int cfg, const mh_tensor5* in_, const float* packed_w, const float* bias, const mh_tensor5* out_, float* stats, void* stream, bool accumulate,
                             const PoolOut* pool = nullptr);
-// can mh_conv3d_k3_pool_f32 serve this layer?  the split-precision configuration's 16 x 16 regions (not the 8 x 32 shape), even extents, even z-chunks
-int mh_conv3d_k3_pool_accepts(int cfg, int Cin, int Cout, int D, int H, int W);
 int mh_conv3d_k3_pool_f32(int cfg, const mh_tensor5* in_, const float* packed_w, const float* bias, const mh_tensor5* out_, float* stats, float* pool_max, float* pool_min,
                           int64_t pool_n_stride, void* stream) {
     if (!in_ || !out_ || !pool_max || !pool_min || !stats || !in_->nrm) return fail(MH_ERR_ARG, "conv3d_k3_pool: input records, statistics and both pooled tensors are required");
@@ -721,10 +705,9 @@ static int conv3d_k3_launch(int cfg, const mh_tensor5* in_, const float* packed_
         // reads but need 128 registers + 36 bytes of scratch: 1.86 ms; gpurun_out/r3first -> profiles/r03_c1_cot_ab.txt)
         constexpr int cot = 8;
         const dim3 grid((unsigned)(txn * tyn * cdiv(out.D, zc)), (unsigned)(out.C / cot), (unsigned)out.N);
-        if (stats && in.nrm) hipLaunchKernelGGL((conv3d_k3_c1_kernel<cot, true, true>), grid, dim3(256), 0, s, in, packed_w, bias, out, stats, txn, tyn, zc);
-        else if (stats) hipLaunchKernelGGL((conv3d_k3_c1_kernel<cot, true, false>), grid, dim3(256), 0, s, in, packed_w, bias, out, stats, txn, tyn, zc);
-        else if (in.nrm) hipLaunchKernelGGL((conv3d_k3_c1_kernel<cot, false, true>), grid, dim3(256), 0, s, in, packed_w, bias, out, stats, txn, tyn, zc);
-        else hipLaunchKernelGGL((conv3d_k3_c1_kernel<cot, false, false>), grid, dim3(256), 0, s, in, packed_w, bias, out, stats, txn, tyn, zc);
+        with_flags([&](auto ST, auto NRM) {
+            hipLaunchKernelGGL((conv3d_k3_c1_kernel<cot, ST, NRM>), grid, dim3(256), 0, s, in, packed_w, bias, out, stats, txn, tyn, zc);
+        }, stats != nullptr, in.nrm != nullptr);
         return launched("conv3d_k3_c1");
     }
     if (cfg == MH_CFG_H2W) {
@@ -741,10 +724,16 @@ static int conv3d_k3_launch(int cfg, const mh_tensor5* in_, const float* packed_
         const dim3 grid((unsigned)total);
         const uint4* wq = reinterpret_cast<const uint4*>(packed_w);
         const float* tail = packed_w + (mh_conv3d_k3_packed_floats(cfg, in.C, out.C) - H2_TAIL);
-        if (pool) hipLaunchKernelGGL((conv3d_k3_h2w_kernel<true, false, true>), grid, dim3(64 * HWG_WAVES), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, pool->mx, pool->mn, pool->n_stride);
-        else if (accumulate) hipLaunchKernelGGL((conv3d_k3_h2w_kernel<true, true, false>), grid, dim3(64 * HWG_WAVES), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, (float*)nullptr, (float*)nullptr, 0LL);
-        else if (stats) hipLaunchKernelGGL((conv3d_k3_h2w_kernel<true, false, false>), grid, dim3(64 * HWG_WAVES), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, (float*)nullptr, (float*)nullptr, 0LL);
-        else hipLaunchKernelGGL((conv3d_k3_h2w_kernel<false, false, false>), grid, dim3(64 * HWG_WAVES), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, (float*)nullptr, (float*)nullptr, 0LL);
+        auto launch = [&](auto ST, auto ACC, auto POOL) {      // four forms exist: plain, statistics, accumulating, pooling
+            hipLaunchKernelGGL((conv3d_k3_h2w_kernel<ST, ACC, POOL>), grid, dim3(64 * HWG_WAVES), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk,
+                               pool ? pool->mx : (float*)nullptr, pool ? pool->mn : (float*)nullptr, pool ? pool->n_stride : 0LL);
+        };
+        const std::true_type yes;
+        const std::false_type no;
+        if (pool) launch(yes, no, yes);
+        else if (accumulate) launch(yes, yes, no);
+        else if (stats) launch(yes, no, no);
+        else launch(no, no, no);
         return launched("conv3d_k3_h2w");
     }
     if (cfg == MH_CFG_H2V) {
@@ -760,13 +749,9 @@ static int conv3d_k3_launch(int cfg, const mh_tensor5* in_, const float* packed_
         const uint4* wq = reinterpret_cast<const uint4*>(packed_w);
         const float* tail = packed_w + (mh_conv3d_k3_packed_floats(cfg, in.C, out.C) - H2_TAIL);
         const dim3 grid((unsigned)total);
-        if (ncgw == 2) {
-            if (stats) hipLaunchKernelGGL((conv3d_k3_vol_h2_kernel<2, true>), grid, dim3(HV_NT), 0, s, in, wq, tail, bias, out, stats);
-            else hipLaunchKernelGGL((conv3d_k3_vol_h2_kernel<2, false>), grid, dim3(HV_NT), 0, s, in, wq, tail, bias, out, stats);
-        } else {
-            if (stats) hipLaunchKernelGGL((conv3d_k3_vol_h2_kernel<1, true>), grid, dim3(HV_NT), 0, s, in, wq, tail, bias, out, stats);
-            else hipLaunchKernelGGL((conv3d_k3_vol_h2_kernel<1, false>), grid, dim3(HV_NT), 0, s, in, wq, tail, bias, out, stats);
-        }
+        with_int<1, 2>(ncgw, [&](auto NCG) {
+            with_flags([&](auto ST) { hipLaunchKernelGGL((conv3d_k3_vol_h2_kernel<NCG, ST>), grid, dim3(HV_NT), 0, s, in, wq, tail, bias, out, stats); }, stats != nullptr);
+        });
         return launched("conv3d_k3_vol_h2");
     }
     if (cfg == MH_CFG_H2 || cfg == MH_CFG_H2C) {
@@ -786,39 +771,23 @@ static int conv3d_k3_launch(int cfg, const mh_tensor5* in_, const float* packed_
         const dim3 grid((unsigned)total);
         const uint4* wq = reinterpret_cast<const uint4*>(packed_w);
         const float* tail = packed_w + (mh_conv3d_k3_packed_floats(cfg, in.C, out.C) - H2_TAIL);
-#define MH_H2_LAUNCH(RES_, WIDE_, C16_)                                                                                                                  \
-    {                                                                                                                                                \
-        if (stats && in.nrm) hipLaunchKernelGGL((conv3d_k3_h2_kernel<true, true, RES_, WIDE_, C16_>), grid, dim3(512), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, (float*)nullptr, (float*)nullptr, 0LL);   \
-        else if (stats) hipLaunchKernelGGL((conv3d_k3_h2_kernel<true, false, RES_, WIDE_, C16_>), grid, dim3(512), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, (float*)nullptr, (float*)nullptr, 0LL);       \
-        else if (in.nrm) hipLaunchKernelGGL((conv3d_k3_h2_kernel<false, true, RES_, WIDE_, C16_>), grid, dim3(512), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, (float*)nullptr, (float*)nullptr, 0LL);      \
-        else hipLaunchKernelGGL((conv3d_k3_h2_kernel<false, false, RES_, WIDE_, C16_>), grid, dim3(512), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, (float*)nullptr, (float*)nullptr, 0LL);                 \
-    }
+        const bool res = in.C <= 2 * H2_KC;
         if (pool) {             // MaxPool3d(2) of the following block leaves with the result (kernels/conv3d_h2.h, POOL): 16 x 16 regions, statistics and records present
-#define MH_H2_POOL(RES_) hipLaunchKernelGGL((conv3d_k3_h2_kernel<true, true, RES_, false, false, false, true>), grid, dim3(512), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, pool->mx, pool->mn, pool->n_stride)
-            if (in.C <= 2 * H2_KC) MH_H2_POOL(true); else MH_H2_POOL(false);
-#undef MH_H2_POOL
+            with_flags([&](auto RES) {
+                hipLaunchKernelGGL((conv3d_k3_h2_kernel<true, true, RES, false, false, false, true>), grid, dim3(512), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, pool->mx, pool->mn, pool->n_stride);
+            }, res);
             return launched("conv3d_k3_h2_pool");
         }
         if (accumulate) {       // out += conv (kernels/conv3d_h2.h, ACC): statistics and input records present (checked by the entry point)
-#define MH_H2_ACC(RES_, WIDE_, C16_) hipLaunchKernelGGL((conv3d_k3_h2_kernel<true, true, RES_, WIDE_, C16_, true>), grid, dim3(512), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, (float*)nullptr, (float*)nullptr, 0LL)
-            if (c16) {          // round 6: SegResNet's residual joins at its 16-channel level (x += conv2(...), statistics of the sum)
-                if (in.C <= 2 * H2_KC) { if (wide) MH_H2_ACC(true, true, true); else MH_H2_ACC(true, false, true); }
-                else { if (wide) MH_H2_ACC(false, true, true); else MH_H2_ACC(false, false, true); }
-            } else {
-                if (in.C <= 2 * H2_KC) { if (wide) MH_H2_ACC(true, true, false); else MH_H2_ACC(true, false, false); }
-                else { if (wide) MH_H2_ACC(false, true, false); else MH_H2_ACC(false, false, false); }
-            }
-#undef MH_H2_ACC
+            // round 6: with C16, SegResNet's residual joins at its 16-channel level (x += conv2(...), statistics of the sum)
+            with_flags([&](auto RES, auto WIDE, auto C16) {
+                hipLaunchKernelGGL((conv3d_k3_h2_kernel<true, true, RES, WIDE, C16, true>), grid, dim3(512), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, (float*)nullptr, (float*)nullptr, 0LL);
+            }, res, wide, c16);
             return launched("conv3d_k3_h2_acc");
         }
-        if (c16) {
-            if (in.C <= 2 * H2_KC) { if (wide) MH_H2_LAUNCH(true, true, true) else MH_H2_LAUNCH(true, false, true) }
-            else { if (wide) MH_H2_LAUNCH(false, true, true) else MH_H2_LAUNCH(false, false, true) }
-        } else {
-            if (in.C <= 2 * H2_KC) { if (wide) MH_H2_LAUNCH(true, true, false) else MH_H2_LAUNCH(true, false, false) }
-            else { if (wide) MH_H2_LAUNCH(false, true, false) else MH_H2_LAUNCH(false, false, false) }
-        }
-#undef MH_H2_LAUNCH
+        with_flags([&](auto ST, auto NRM, auto RES, auto WIDE, auto C16) {
+            hipLaunchKernelGGL((conv3d_k3_h2_kernel<ST, NRM, RES, WIDE, C16>), grid, dim3(512), 0, s, in, wq, tail, bias, out, stats, bxn, byn, zc, nblk, (float*)nullptr, (float*)nullptr, 0LL);
+        }, stats != nullptr, in.nrm != nullptr, res, wide, c16);
         return launched(c16 ? "conv3d_k3_h2c" : "conv3d_k3_h2");
     }
     if (cfg == MH_CFG_WINO2D) {
@@ -834,10 +803,9 @@ static int conv3d_k3_launch(int cfg, const mh_tensor5* in_, const float* packed_
         const dim3 grid((unsigned)total);
         // conv3d_wino2p.h: two 256-register waves per SIMD, the Winograd positions split over the pair (17.7-17.9 ms for 32 -> 32 ch @ 96^3 x 64 windows;
         // the one-wave form of round 1 and the matrix-wave + staging-wave form measured 18.7-18.9 ms, profiles/r02_wino2_impls.json, and were removed)
-        if (stats && in.nrm) hipLaunchKernelGGL((conv3d_k3_wino2p_kernel<true, true>), grid, dim3(512), 0, s, in, packed_w, bias, out, stats, bxn, byn, zc, nblk);
-        else if (stats) hipLaunchKernelGGL((conv3d_k3_wino2p_kernel<true, false>), grid, dim3(512), 0, s, in, packed_w, bias, out, stats, bxn, byn, zc, nblk);
-        else if (in.nrm) hipLaunchKernelGGL((conv3d_k3_wino2p_kernel<false, true>), grid, dim3(512), 0, s, in, packed_w, bias, out, stats, bxn, byn, zc, nblk);
-        else hipLaunchKernelGGL((conv3d_k3_wino2p_kernel<false, false>), grid, dim3(512), 0, s, in, packed_w, bias, out, stats, bxn, byn, zc, nblk);
+        with_flags([&](auto ST, auto NRM) {
+            hipLaunchKernelGGL((conv3d_k3_wino2p_kernel<ST, NRM>), grid, dim3(512), 0, s, in, packed_w, bias, out, stats, bxn, byn, zc, nblk);
+        }, stats != nullptr, in.nrm != nullptr);
         return launched("conv3d_k3_wino2p");
     }
     if (cfg == 0) {
@@ -847,27 +815,12 @@ static int conv3d_k3_launch(int cfg, const mh_tensor5* in_, const float* packed_
         hipLaunchKernelGGL((conv3d_k3_direct_kernel<COT>), grid, dim3(256), 0, s, in, packed_w, bias, out);
         return launched("conv3d_k3_direct");
     }
-    const CfgInfo& k = kCfg[cfg];
-    (void)k;
     if (!mh_conv3d_k3_accepts(cfg, in.C, out.C))
         return fail(MH_ERR_ARG, "conv3d_k3: configuration %d does not take Cin=%d Cout=%d", cfg, in.C, out.C);
     if (!aligned(packed_w, 16)) return fail(MH_ERR_ARG, "conv3d_k3: packed weights must be 16-byte aligned");
-    switch (cfg) {
-        case 1: launch_mfma<Cfg1>(in, packed_w, bias, out, stats, s); break;
-        case 2: launch_mfma<Cfg2>(in, packed_w, bias, out, stats, s); break;
-        case 3: launch_mfma<Cfg3>(in, packed_w, bias, out, stats, s); break;
-        case 4: launch_mfma<Cfg4>(in, packed_w, bias, out, stats, s); break;
-        case 5: launch_mfma<Cfg5>(in, packed_w, bias, out, stats, s); break;
-        case 6: launch_mfma<Cfg6>(in, packed_w, bias, out, stats, s); break;
-        case 7: launch_mfma<Cfg7>(in, packed_w, bias, out, stats, s); break;
-        case 8: launch_mfma<Cfg8>(in, packed_w, bias, out, stats, s); break;
-        case 9: launch_mfma<Cfg9>(in, packed_w, bias, out, stats, s); break;
-        case 10: launch_mfma<Cfg10>(in, packed_w, bias, out, stats, s); break;
-        case 11: launch_mfma<Cfg11>(in, packed_w, bias, out, stats, s); break;
-        case 12: launch_mfma<Cfg12>(in, packed_w, bias, out, stats, s); break;
-        case 13: launch_mfma<Cfg13>(in, packed_w, bias, out, stats, s); break;
-        case 14: launch_mfma<Cfg14>(in, packed_w, bias, out, stats, s); break;
-    }
+    with_type<Cfg1, Cfg2, Cfg3, Cfg4, Cfg5, Cfg6, Cfg7, Cfg8, Cfg9, Cfg10, Cfg11, Cfg12, Cfg13, Cfg14>(cfg - 1, [&](auto CFG) {
+        launch_mfma<MH_TYPE(CFG)>(in, packed_w, bias, out, stats, s);
+    });
     return launched("conv3d_k3_mfma");
 }
 
@@ -921,13 +874,9 @@ int mh_maxpool2_f32(const mh_tensor5* in_, const mh_tensor5* out_, void* stream)
     const dim3 grid(blocks_for((long long)out.D * out.H * out.W), (unsigned)out.C, (unsigned)out.N);
     const bool pair = in.W % 2 == 0 && aligned(in.data, 8) && in.n_stride % 2 == 0;
     const bool planar = out.D == in.D && out.D != in.D / 2;      // in.D == 1 (a 2-D network's plane): 1 / 2 == 0, so this is unambiguous
-    if (planar) {
-        if (pair) hipLaunchKernelGGL((maxpool2_kernel<true, 1>), grid, dim3(256), 0, (hipStream_t)stream, in, out);
-        else hipLaunchKernelGGL((maxpool2_kernel<false, 1>), grid, dim3(256), 0, (hipStream_t)stream, in, out);
-    } else {
-        if (pair) hipLaunchKernelGGL((maxpool2_kernel<true, 2>), grid, dim3(256), 0, (hipStream_t)stream, in, out);
-        else hipLaunchKernelGGL((maxpool2_kernel<false, 2>), grid, dim3(256), 0, (hipStream_t)stream, in, out);
-    }
+    with_int<1, 2>(planar ? 1 : 2, [&](auto ZS) {
+        with_flags([&](auto PAIR) { hipLaunchKernelGGL((maxpool2_kernel<PAIR, ZS>), grid, dim3(256), 0, (hipStream_t)stream, in, out); }, pair);
+    });
     return launched("maxpool2");
 }
 
@@ -951,8 +900,9 @@ int mh_deconv_k2s2_f32(const mh_tensor5* in_, const float* w, const float* bias,
 #endif
     // 4 output channels per thread: 2.13 / 0.46 / 0.24 ms on the BasicUNet decoder shapes against 2.42 / 0.56 / 0.27 with 8 (fewer channel planes written at once,
     // twice the workgroups; two voxels per thread with 16-byte stores measured slower: profiles/r03_deconv_variants.json)
-    if (out.C % 4 == 0) hipLaunchKernelGGL((deconv_k2s2_kernel<4, true>), dim3(nb, (unsigned)(out.C / 4), (unsigned)out.N), dim3(256), 0, (hipStream_t)stream, in, w, bias, out);
-    else hipLaunchKernelGGL((deconv_k2s2_kernel<4, false>), dim3(nb, (unsigned)cdiv(out.C, 4), (unsigned)out.N), dim3(256), 0, (hipStream_t)stream, in, w, bias, out);
+    with_flags([&](auto WHOLE) {
+        hipLaunchKernelGGL((deconv_k2s2_kernel<4, WHOLE>), dim3(nb, (unsigned)cdiv(out.C, 4), (unsigned)out.N), dim3(256), 0, (hipStream_t)stream, in, w, bias, out);
+    }, out.C % 4 == 0);
     return launched("deconv_k2s2");
 }
 
@@ -989,8 +939,9 @@ int mh_deconv_k2s2_h2_f32(const mh_tensor5* in_, const float* packed, const floa
     const float* tail = packed + (mh_deconv_k2s2_h2_packed_floats(in.C, out.C) - H2_TAIL);
     const unsigned nb = (unsigned)(((long long)in.D * in.H * in.W + 127) / 128);
     hipStream_t s = (hipStream_t)stream;
-    if (out.C % 32 == 0) hipLaunchKernelGGL((deconv_k2s2_h2_kernel<8>), dim3(nb, (unsigned)(out.C / 32), (unsigned)out.N), dim3(256), 0, s, in, wq, tail, bias, out);
-    else hipLaunchKernelGGL((deconv_k2s2_h2_kernel<4>), dim3(nb, (unsigned)(out.C / 16), (unsigned)out.N), dim3(256), 0, s, in, wq, tail, bias, out);
+    with_int<4, 8>(out.C % 32 == 0 ? 8 : 4, [&](auto MT) {       // 4 * MT output channels per workgroup
+        hipLaunchKernelGGL((deconv_k2s2_h2_kernel<MT>), dim3(nb, (unsigned)(out.C / (4 * MT)), (unsigned)out.N), dim3(256), 0, s, in, wq, tail, bias, out);
+    });
     return launched("deconv_k2s2_h2");
 }
 
@@ -1035,9 +986,11 @@ int mh_upconv_k4s2_f32(const mh_tensor5* low_, const float* packed, const float*
     const float* tail = packed + (mh_upconv_k4s2_packed_floats(low.C, out.C) - H2_TAIL);
     hipStream_t s = (hipStream_t)stream;
     const dim3 g((unsigned)total), bl(UC_NT);
-    if (!accumulate) hipLaunchKernelGGL((upconv_k4s2_h2_kernel<false, false>), g, bl, 0, s, low, wq, tail, bias_table, out, stats, txn, tyn, zc, nblk);
-    else if (stats) hipLaunchKernelGGL((upconv_k4s2_h2_kernel<true, true>), g, bl, 0, s, low, wq, tail, bias_table, out, stats, txn, tyn, zc, nblk);
-    else hipLaunchKernelGGL((upconv_k4s2_h2_kernel<false, true>), g, bl, 0, s, low, wq, tail, bias_table, out, stats, txn, tyn, zc, nblk);
+    auto launch = [&](auto ST, auto ACC) {      // three forms exist: statistics are those of the sum
+        hipLaunchKernelGGL((upconv_k4s2_h2_kernel<ST, ACC>), g, bl, 0, s, low, wq, tail, bias_table, out, stats, txn, tyn, zc, nblk);
+    };
+    if (!accumulate) launch(std::false_type{}, std::false_type{});
+    else with_flags([&](auto ST) { launch(ST, std::true_type{}); }, stats != nullptr);
     return launched("upconv_k4s2");
 }
 
@@ -1112,29 +1065,12 @@ int mh_conv3d_k3s2_f32(const mh_tensor5* in_, const float* packed, const float* 
     const uint4* wq = reinterpret_cast<const uint4*>(packed);
     const float* tail = packed + (mh_conv3d_k3s2_packed_floats(in.C, out.C) - H2_TAIL);
     const dim3 g((unsigned)total), bl(S2_NT);
-#define MH_S2_LAUNCH(NCG_, F_)                                                                                                                          \
-    {                                                                                                                                                   \
-        if (stats) hipLaunchKernelGGL((conv3d_k3s2_h2_kernel<NCG_, true, F_>), g, bl, 0, s, in, xs, expo, wq, tail, bias, out, stats, t.tr, t.tc, t.txn, t.tyn, zc, nblk);  \
-        else hipLaunchKernelGGL((conv3d_k3s2_h2_kernel<NCG_, false, F_>), g, bl, 0, s, in, xs, expo, wq, tail, bias, out, stats, t.tr, t.tc, t.txn, t.tyn, zc, nblk);        \
-    }
-    if (fused) { if (ncgw == 2) MH_S2_LAUNCH(2, true) else MH_S2_LAUNCH(1, true) }
-    else { if (ncgw == 2) MH_S2_LAUNCH(2, false) else MH_S2_LAUNCH(1, false) }
-#undef MH_S2_LAUNCH
+    with_int<1, 2>(ncgw, [&](auto NCG) {
+        with_flags([&](auto ST, auto FUSED) {
+            hipLaunchKernelGGL((conv3d_k3s2_h2_kernel<NCG, ST, FUSED>), g, bl, 0, s, in, xs, expo, wq, tail, bias, out, stats, t.tr, t.tc, t.txn, t.tyn, zc, nblk);
+        }, stats != nullptr, fused != 0);
+    });
     return launched("conv3d_k3s2");
-}
-
-template <int VEC, bool STATS>
-static void launch_1x1(int co, unsigned nb, unsigned nbatch, hipStream_t s, const Tensor& in, const float* w, const float* bias,
-                       const Tensor& out, int co0, float* stats) {
-#define MH_1X1_CASE(CO)                                                                                               \
-    case CO:                                                                                                          \
-        hipLaunchKernelGGL((conv1x1_kernel<CO, VEC, STATS>), dim3(nb, nbatch), dim3(256), 0, s, in, w, bias, out, co0, stats, (int)nb);      \
-        break;
-    switch (co) {
-        MH_1X1_CASE(1) MH_1X1_CASE(2) MH_1X1_CASE(3) MH_1X1_CASE(4)
-        MH_1X1_CASE(5) MH_1X1_CASE(6) MH_1X1_CASE(7) MH_1X1_CASE(8) MH_1X1_CASE(16)
-    }
-#undef MH_1X1_CASE
 }
 
 // one {count, mean, M2} record per (n, cout, workgroup): the tile count of a stats-fused 1x1x1 convolution (mh_conv1x1_stats_f32) on a D x H x W plane
@@ -1154,13 +1090,13 @@ static int conv1x1_impl(const mh_tensor5* in_, const float* w, const float* bias
     for (int co0 = 0; co0 < out.C;) {      // 16 output channels per pass where they exist (the input is read once per pass)
         const int left = out.C - co0;
         const int co = left >= 16 ? 16 : left < 8 ? left : 8;
-        if (stats) {
-            if (v4) launch_1x1<4, true>(co, nb, (unsigned)in.N, (hipStream_t)stream, in, w, bias, out, co0, stats);
-            else launch_1x1<1, true>(co, nb, (unsigned)in.N, (hipStream_t)stream, in, w, bias, out, co0, stats);
-        } else {
-            if (v4) launch_1x1<4, false>(co, nb, (unsigned)in.N, (hipStream_t)stream, in, w, bias, out, co0, nullptr);
-            else launch_1x1<1, false>(co, nb, (unsigned)in.N, (hipStream_t)stream, in, w, bias, out, co0, nullptr);
-        }
+        with_int<1, 2, 3, 4, 5, 6, 7, 8, 16>(co, [&](auto CO) {
+            with_int<1, 4>(v4 ? 4 : 1, [&](auto VEC) {
+                with_flags([&](auto ST) {
+                    hipLaunchKernelGGL((conv1x1_kernel<CO, VEC, ST>), dim3(nb, (unsigned)in.N), dim3(256), 0, (hipStream_t)stream, in, w, bias, out, co0, stats, (int)nb);
+                }, stats != nullptr);
+            });
+        });
         co0 += co;
     }
     return launched("conv1x1");
@@ -1210,12 +1146,9 @@ int mh_conv1x1_h2_f32(const mh_tensor5* in_, const float* packed, const float* b
     for (int co0 = 0, pass = 0; co0 < out.C; co0 += 64, ++pass) {
         const uint4* wq = reinterpret_cast<const uint4*>(packed) + (long long)pass * nks * C1H_SLAB;
         const bool two = out.C - co0 > 32;
-#define MH_C1H_LAUNCH(MT_, ST_) hipLaunchKernelGGL((conv1x1_h2_kernel<MT_, ST_>), grid, dim3(512), 0, s, in, wq, tail, bias, out, co0, stats, tiles)
-        if (two && stats) MH_C1H_LAUNCH(2, true);
-        else if (two) MH_C1H_LAUNCH(2, false);
-        else if (stats) MH_C1H_LAUNCH(1, true);
-        else MH_C1H_LAUNCH(1, false);
-#undef MH_C1H_LAUNCH
+        with_int<1, 2>(two ? 2 : 1, [&](auto MT) {
+            with_flags([&](auto ST) { hipLaunchKernelGGL((conv1x1_h2_kernel<MT, ST>), grid, dim3(512), 0, s, in, wq, tail, bias, out, co0, stats, tiles); }, stats != nullptr);
+        });
     }
     return launched("conv1x1_h2");
 }
@@ -1236,9 +1169,9 @@ int mh_conv1x1_windows_f32(const mh_tensor5* in_, const float* w, const float* b
             pl.off[i] = place[4 * (n0 + i)]; pl.sc[i] = place[4 * (n0 + i) + 1]; pl.sd[i] = place[4 * (n0 + i) + 2]; pl.sh[i] = place[4 * (n0 + i) + 3];
         }
         const dim3 grid(blocks_for(DHW / 4), (unsigned)nn);
-#define MH_1W_CASE(CO) case CO: hipLaunchKernelGGL((conv1x1_windows_kernel<CO>), grid, dim3(256), 0, (hipStream_t)stream, in, w, bias, base, pl, n0); break;
-        switch (Cout) { MH_1W_CASE(1) MH_1W_CASE(2) MH_1W_CASE(3) MH_1W_CASE(4) MH_1W_CASE(5) MH_1W_CASE(6) MH_1W_CASE(7) MH_1W_CASE(8) }
-#undef MH_1W_CASE
+        with_int<1, 2, 3, 4, 5, 6, 7, 8>(Cout, [&](auto CO) {
+            hipLaunchKernelGGL((conv1x1_windows_kernel<CO>), grid, dim3(256), 0, (hipStream_t)stream, in, w, bias, base, pl, n0);
+        });
     }
     return launched("conv1x1_windows");
 }
@@ -1287,6 +1220,11 @@ static int stream_chunks(long long units, int Do, int slots, int prime, int min_
 }
 
 
+// Two forms of the stream kernel that no path launches (4 loads per lane at 256 threads) but that belong to the library's kernel set: the dispatch in
+// mh_affine_resample_f32 names only the (NLOAD, NT) pairs it can reach, so they are instantiated here.  Dropping them changes which kernels exist.
+[[maybe_unused]] static const void* const kStreamFormsNeverLaunched[] = {(const void*)&separable_resample_stream_kernel<double, 4, 256, true, 3>,
+                                                                        (const void*)&separable_resample_stream_kernel<float, 4, 256, true, 0>};
+
 int64_t mh_affine_resample_workspace_bytes(int Do, int Ho, int Wo) { return (int64_t)(Do + Ho + Wo) * (int64_t)sizeof(AxisTap<double>); }
 
 int mh_affine_resample_f32(const float* src, int NC, int Di, int Hi, int Wi, float* dst, int Do, int Ho, int Wo, const double* m,
@@ -1315,71 +1253,60 @@ int mh_affine_resample_f32(const float* src, int NC, int Di, int Hi, int Wi, flo
             // 0.253-0.267 vs 0.291-0.305 ms per 512^3 volume; fp64 interpolation (the reference default) measures the same either
             // way (0.277-0.299 ms) and keeps 256.  MONAI_AMD_RS_THREADS=256|512 overrides.
             const bool wide = knob_int("MONAI_AMD_RS_THREADS", compute_f64 ? 256 : 512) != 256;
-            static int slots[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};     // [wide][f64][small]
-            int& sl = slots[wide ? 1 : 0][compute_f64 ? 1 : 0][small ? 1 : 0];
             // round 6 (kernels/resample.h, profiles/r06_resample_variants.txt): four consecutive x per lane and one 16-byte store per row (VEC) in every form; the fp64 form
             // of 256 threads takes its source planes by LDS-DMA into a ring of three slots (RING = 3: 0.281 -> 0.270 ms at config 4; the fp32 form does not gain from it).
             // MONAI_AMD_RS_RING=0 in the development build keeps the register prefetch
             static const bool ring = knob_int("MONAI_AMD_RS_RING", 1) != 0;
             const bool use_ring = ring && compute_f64 && !wide;
-#define MH_RS_STREAM(T_, NL_, NT_, TAB_)                                                                                                              \
-    if (use_ring && (NT_) == 256) hipLaunchKernelGGL((separable_resample_stream_kernel<T_, NL_, 256, true, sizeof(T_) == 8 ? 3 : 0>), g, dim3(256), 0, s, src, dst, TAB_, a, zchunk, nchunk); \
-    else hipLaunchKernelGGL((separable_resample_stream_kernel<T_, NL_, NT_, true, 0>), g, dim3(NT_), 0, s, src, dst, TAB_, a, zchunk, nchunk)
-#define MH_RS_SLOTS(T_, NL_, NT_) ((use_ring && (NT_) == 256) ? resident_wgs(separable_resample_stream_kernel<T_, NL_, 256, true, sizeof(T_) == 8 ? 3 : 0>, 256) \
-                                                             : resident_wgs(separable_resample_stream_kernel<T_, NL_, NT_, true, 0>, NT_))
-            if (sl == 0) {
-                if (wide) sl = compute_f64 ? (small ? MH_RS_SLOTS(double, 4, 512) : MH_RS_SLOTS(double, 8, 512)) : (small ? MH_RS_SLOTS(float, 4, 512) : MH_RS_SLOTS(float, 8, 512));
-                else sl = compute_f64 ? (small ? MH_RS_SLOTS(double, 8, 256) : MH_RS_SLOTS(double, 16, 256)) : (small ? MH_RS_SLOTS(float, 8, 256) : MH_RS_SLOTS(float, 16, 256));
-            }
-            int nchunk = stream_chunks(tiles * NC, Do, sl, 1, 8, "MONAI_AMD_RS_CHUNKS");
-            if (!compute_f64 && wide && !knob_str("MONAI_AMD_RS_CHUNKS")) {
-                // round 6 (profiles/r06_resample_variants.txt): with four workgroups of the fp32 form per CU the launch wants MANY rounds of workgroups, not whole ones --
-                // 512^3 -> 410 x 410 x 819: 11 chunks (2 rounds) 0.279 ms, 21: 0.256, 41: 0.237, 52: 0.236; the fp64 form is flat over the same sweep and keeps the rule above.
-                // >= 7 rounds of the resident slots, z-chunks of at least 8 planes
-                const long long units = tiles * NC;
-                long long want = (7LL * sl + units - 1) / units;
-                const int maxc = Do / 8 < 1 ? 1 : Do / 8;
-                want = want < 1 ? 1 : (want > maxc ? maxc : want);
-                if ((int)want > nchunk) nchunk = (int)want;
-            }
-            if (use_ring && !knob_str("MONAI_AMD_RS_CHUNKS")) {      // the ring form: 11 chunks 0.310 ms, 21: 0.279, 26: 0.270, 41: 0.283 -- about 4.5 rounds of the resident slots
-                const long long units = tiles * NC;
-                long long want = (9LL * sl + 2 * units - 1) / (2 * units);
-                const int maxc = Do / 8 < 1 ? 1 : Do / 8;
-                want = want < 1 ? 1 : (want > maxc ? maxc : want);
-                if ((int)want > nchunk) nchunk = (int)want;
-            }
-            const int zchunk = cdiv(Do, nchunk);
-            nchunk = cdiv(Do, zchunk);
-            const long long nwg = tiles * nchunk * NC;
-            if (nwg > 0x7fffffffLL) return fail(MH_ERR_UNSUPPORTED, "affine_resample: problem too large for one launch");
-            const dim3 g((unsigned)nwg);
-            if (compute_f64) {
-                AxisTap<double>* tab = static_cast<AxisTap<double>*>(workspace);
-                hipLaunchKernelGGL((resample_axis_table_kernel<double>), dim3(tb), dim3(256), 0, s, tab, a);
-                const AxisTap<double>* ct = tab;
-                if (wide) { if (small) MH_RS_STREAM(double, 4, 512, ct); else MH_RS_STREAM(double, 8, 512, ct); }
-                else { if (small) MH_RS_STREAM(double, 8, 256, ct); else MH_RS_STREAM(double, 16, 256, ct); }
-            } else {
-                AxisTap<float>* tab = static_cast<AxisTap<float>*>(workspace);
-                hipLaunchKernelGGL((resample_axis_table_kernel<float>), dim3(tb), dim3(256), 0, s, tab, a);
-                const AxisTap<float>* ct = tab;
-                if (wide) { if (small) MH_RS_STREAM(float, 4, 512, ct); else MH_RS_STREAM(float, 8, 512, ct); }
-                else { if (small) MH_RS_STREAM(float, 8, 256, ct); else MH_RS_STREAM(float, 16, 256, ct); }
-            }
-#undef MH_RS_SLOTS
-#undef MH_RS_STREAM
+            // `kernel` is the instantiation chosen below, `sl` its own cache of resident workgroups: the occupancy query and the launch share the one pointer
+            auto run = [&](auto kernel, int nt, int& sl, auto T) -> int {
+                using real = MH_TYPE(T);
+                if (sl == 0) sl = resident_wgs(kernel, nt);
+                int nchunk = stream_chunks(tiles * NC, Do, sl, 1, 8, "MONAI_AMD_RS_CHUNKS");
+                if (!compute_f64 && wide && !knob_str("MONAI_AMD_RS_CHUNKS")) {
+                    // round 6 (profiles/r06_resample_variants.txt): with four workgroups of the fp32 form per CU the launch wants MANY rounds of workgroups, not whole ones --
+                    // 512^3 -> 410 x 410 x 819: 11 chunks (2 rounds) 0.279 ms, 21: 0.256, 41: 0.237, 52: 0.236; the fp64 form is flat over the same sweep and keeps the rule above.
+                    // >= 7 rounds of the resident slots, z-chunks of at least 8 planes
+                    const long long units = tiles * NC;
+                    long long want = (7LL * sl + units - 1) / units;
+                    const int maxc = Do / 8 < 1 ? 1 : Do / 8;
+                    want = want < 1 ? 1 : (want > maxc ? maxc : want);
+                    if ((int)want > nchunk) nchunk = (int)want;
+                }
+                if (use_ring && !knob_str("MONAI_AMD_RS_CHUNKS")) {      // the ring form: 11 chunks 0.310 ms, 21: 0.279, 26: 0.270, 41: 0.283 -- about 4.5 rounds of the resident slots
+                    const long long units = tiles * NC;
+                    long long want = (9LL * sl + 2 * units - 1) / (2 * units);
+                    const int maxc = Do / 8 < 1 ? 1 : Do / 8;
+                    want = want < 1 ? 1 : (want > maxc ? maxc : want);
+                    if ((int)want > nchunk) nchunk = (int)want;
+                }
+                const int zchunk = cdiv(Do, nchunk);
+                nchunk = cdiv(Do, zchunk);
+                const long long nwg = tiles * nchunk * NC;
+                if (nwg > 0x7fffffffLL) return fail(MH_ERR_UNSUPPORTED, "affine_resample: problem too large for one launch");
+                AxisTap<real>* tab = static_cast<AxisTap<real>*>(workspace);
+                hipLaunchKernelGGL((resample_axis_table_kernel<real>), dim3(tb), dim3(256), 0, s, tab, a);
+                hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(nt), 0, s, src, dst, (const AxisTap<real>*)tab, a, zchunk, nchunk);
+                return MH_OK;
+            };
+            int rc = MH_OK;
+            with_type<float, double>(compute_f64 ? 1 : 0, [&](auto T) {
+                with_flags([&](auto WIDE, auto SMALL, auto RING) {
+                    // the (NLOAD, NT) pairs that exist: (4, 512), (8, 512), (8, 256), (16, 256); RING = 3 only for double at 256 threads
+                    constexpr int NT = WIDE ? 512 : 256, NLOAD = (WIDE ? 4 : 8) * (SMALL ? 1 : 2), RG = RING && !WIDE && sizeof(MH_TYPE(T)) == 8 ? 3 : 0;
+                    static int sl = 0;
+                    rc = run(separable_resample_stream_kernel<MH_TYPE(T), NLOAD, NT, true, RG>, NT, sl, T);
+                }, wide, small, use_ring);
+            });
+            if (rc) return rc;
             return launched("separable_resample_stream");
         }
-        if (compute_f64) {
-            AxisTap<double>* tab = static_cast<AxisTap<double>*>(workspace);
-            hipLaunchKernelGGL((resample_axis_table_kernel<double>), dim3(tb), dim3(256), 0, s, tab, a);
-            hipLaunchKernelGGL((separable_resample_lds_kernel<double>), dim3(nblk), dim3(256), 0, s, src, dst, (const AxisTap<double>*)tab, a);
-        } else {
-            AxisTap<float>* tab = static_cast<AxisTap<float>*>(workspace);
-            hipLaunchKernelGGL((resample_axis_table_kernel<float>), dim3(tb), dim3(256), 0, s, tab, a);
-            hipLaunchKernelGGL((separable_resample_lds_kernel<float>), dim3(nblk), dim3(256), 0, s, src, dst, (const AxisTap<float>*)tab, a);
-        }
+        with_type<float, double>(compute_f64 ? 1 : 0, [&](auto T) {
+            using real = MH_TYPE(T);
+            AxisTap<real>* tab = static_cast<AxisTap<real>*>(workspace);
+            hipLaunchKernelGGL((resample_axis_table_kernel<real>), dim3(tb), dim3(256), 0, s, tab, a);
+            hipLaunchKernelGGL((separable_resample_lds_kernel<real>), dim3(nblk), dim3(256), 0, s, src, dst, (const AxisTap<real>*)tab, a);
+        });
         return launched("separable_resample");
     }
     // general (rotated / sheared) matrices without reflection: the row-mapped kernel with compile-time mode and padding rule
@@ -1388,24 +1315,16 @@ int mh_affine_resample_f32(const float* src, int NC, int Di, int Hi, int Wi, flo
     const bool rows_on = !(rs_general && !strcmp(rs_general, "linear"));
     if (rows_on && i32 && pad != RS_REFLECTION && Do <= 65535 && cdiv(Ho, 4) <= 65535) {
         const dim3 g((unsigned)cdiv(Wo, 64), (unsigned)cdiv(Ho, 4), (unsigned)Do);
-#define MH_RS_ROWS(T_, M_, P_) hipLaunchKernelGGL((affine_resample_rows_kernel<T_, M_, P_>), g, dim3(256), 0, s, src, dst, a)
-#define MH_RS_ROWS_T(T_)                                                                              \
-        {                                                                                             \
-            if (mode == RS_LINEAR) { if (pad == RS_BORDER) MH_RS_ROWS(T_, RS_LINEAR, RS_BORDER); else MH_RS_ROWS(T_, RS_LINEAR, RS_ZEROS); } \
-            else { if (pad == RS_BORDER) MH_RS_ROWS(T_, RS_NEAREST, RS_BORDER); else MH_RS_ROWS(T_, RS_NEAREST, RS_ZEROS); }                 \
-        }
-        if (compute_f64) MH_RS_ROWS_T(double) else MH_RS_ROWS_T(float)
-#undef MH_RS_ROWS_T
-#undef MH_RS_ROWS
+        with_type<float, double>(compute_f64 ? 1 : 0, [&](auto T) {
+            with_int<RS_NEAREST, RS_LINEAR>(mode, [&](auto MODE) {
+                with_int<RS_ZEROS, RS_BORDER>(pad, [&](auto PAD) { hipLaunchKernelGGL((affine_resample_rows_kernel<MH_TYPE(T), MODE, PAD>), g, dim3(256), 0, s, src, dst, a); });
+            });
+        });
         return launched("affine_resample");
     }
-    if (compute_f64) {
-        if (i32) hipLaunchKernelGGL((affine_resample_kernel<double, int>), dim3(nb), dim3(256), 0, s, src, dst, a);
-        else hipLaunchKernelGGL((affine_resample_kernel<double, long long>), dim3(nb), dim3(256), 0, s, src, dst, a);
-    } else {
-        if (i32) hipLaunchKernelGGL((affine_resample_kernel<float, int>), dim3(nb), dim3(256), 0, s, src, dst, a);
-        else hipLaunchKernelGGL((affine_resample_kernel<float, long long>), dim3(nb), dim3(256), 0, s, src, dst, a);
-    }
+    with_type<float, double>(compute_f64 ? 1 : 0, [&](auto T) {
+        with_type<long long, int>(i32 ? 1 : 0, [&](auto IDX) { hipLaunchKernelGGL((affine_resample_kernel<MH_TYPE(T), MH_TYPE(IDX)>), dim3(nb), dim3(256), 0, s, src, dst, a); });
+    });
     return launched("affine_resample");
 }
 
@@ -1421,15 +1340,11 @@ int mh_grid_resample_f32(const float* src, int NC, int Di, int Hi, int Wi, const
     }
     const unsigned nb = blocks_for((long long)Do * Ho * Wo);
     hipStream_t s = (hipStream_t)stream;
-    if (coords_f64) {
-        const double* g = static_cast<const double*>(coords);
-        if (compute_f64) hipLaunchKernelGGL((grid_resample_kernel<double, double>), dim3(nb), dim3(256), 0, s, src, g, dst, a);
-        else hipLaunchKernelGGL((grid_resample_kernel<float, double>), dim3(nb), dim3(256), 0, s, src, g, dst, a);
-    } else {
-        const float* g = static_cast<const float*>(coords);
-        if (compute_f64) hipLaunchKernelGGL((grid_resample_kernel<double, float>), dim3(nb), dim3(256), 0, s, src, g, dst, a);
-        else hipLaunchKernelGGL((grid_resample_kernel<float, float>), dim3(nb), dim3(256), 0, s, src, g, dst, a);
-    }
+    with_type<float, double>(compute_f64 ? 1 : 0, [&](auto T) {
+        with_type<float, double>(coords_f64 ? 1 : 0, [&](auto GT) {
+            hipLaunchKernelGGL((grid_resample_kernel<MH_TYPE(T), MH_TYPE(GT)>), dim3(nb), dim3(256), 0, s, src, static_cast<const MH_TYPE(GT)*>(coords), dst, a);
+        });
+    });
     return launched("grid_resample");
 }
 
@@ -1483,7 +1398,7 @@ int mh_pushpull(const void* source, const void* grid, const void* target, void* 
     if (do_push || do_count)
         if (hipMemsetAsync(out, 0, esz * (size_t)B * (size_t)a.C * X * Y * Z, s) != hipSuccess) return fail(MH_ERR_LAUNCH, "pushpull: memset failed");
     const long long total = (long long)B * Xo * Yo * Zo;
-    if (total > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "pushpull: problem too large for one launch");
+    if (too_large_for(total)) return fail(MH_ERR_UNSUPPORTED, "pushpull: problem too large for one launch");
     const unsigned nb = blocks_for(total);
     int maxo = 0;
     for (int d = 0; d < ndim; ++d) maxo = a.interp[d] > maxo ? a.interp[d] : maxo;
@@ -1492,50 +1407,41 @@ int mh_pushpull(const void* source, const void* grid, const void* target, void* 
     PushPullArgs ag = a;                   // the gathering part of the launch (everything but push / count)
     ag.do_push = 0; ag.do_count = 0;
     const bool gather = ag.do_pull || ag.do_sgrad || ag.do_grad;
-#define MH_PP_LAUNCH1(T_, PATH_, NT_, PULL_)                                                                              \
-    hipLaunchKernelGGL((pushpull_kernel<T_, PATH_, NT_, PULL_>), dim3(nb), dim3(256), 0, s, static_cast<const T_*>(source), \
-                       static_cast<const T_*>(grid), static_cast<const T_*>(target), static_cast<T_*>(out), static_cast<T_*>(grad), ag)
-#define MH_PP_SCATTER(T_, PATH_, NT_)                                                                                        \
-    hipLaunchKernelGGL((pushpull_scatter_kernel<T_, PATH_, NT_>), dim3(nbs), dim3(256), 0, s, static_cast<const T_*>(grid),   \
-                       static_cast<const T_*>(target), static_cast<T_*>(out), a, tx, ty, tz)
-#define MH_PP_LAUNCH(T_, PATH_, NT_)                                    \
-    {                                                                   \
-        if (gather) {                                                   \
-            if (pull_only) MH_PP_LAUNCH1(T_, PATH_, NT_, true);         \
-            else MH_PP_LAUNCH1(T_, PATH_, NT_, false);                  \
-        }                                                               \
-        if (scatter) MH_PP_SCATTER(T_, PATH_, NT_);                     \
-    }
     // scatter modes: a workgroup owns a tile of target voxels (lanes along the last real axis)
     const int tx = ndim == 3 ? 4 : ndim == 2 ? 16 : 256, ty = ndim == 3 ? 4 : ndim == 2 ? 16 : 1, tz = ndim == 3 ? 16 : 1;
     const long long nbs_ll = (long long)B * cdiv(Xo, tx) * cdiv(Yo, ty) * cdiv(Zo, tz);
     if (nbs_ll > 0x7fffffffLL) return fail(MH_ERR_UNSUPPORTED, "pushpull: problem too large for one launch");
     const unsigned nbs = (unsigned)nbs_ll;
-#define MH_PP_PATHS(T_)                                                     \
-    if (a.path == PP_NEAREST) MH_PP_LAUNCH(T_, PP_NEAREST, 1)               \
-    else if (a.path == PP_LINEAR) MH_PP_LAUNCH(T_, PP_LINEAR, 2)            \
-    else if (maxo <= 2) MH_PP_LAUNCH(T_, PP_GENERIC, 3)                     \
-    else if (maxo == 3) MH_PP_LAUNCH(T_, PP_GENERIC, 4)                     \
-    else MH_PP_LAUNCH(T_, PP_GENERIC, 8)
-    if (is_f64) { MH_PP_PATHS(double) } else { MH_PP_PATHS(float) }
-#undef MH_PP_PATHS
-#undef MH_PP_LAUNCH
-#undef MH_PP_SCATTER
-#undef MH_PP_LAUNCH1
+    // the compile-time path and its tap count: nearest 1, linear 2, generic orders <= 2: 3, order 3: 4, beyond: 8
+    const int ntap = a.path == PP_NEAREST ? 1 : a.path == PP_LINEAR ? 2 : maxo <= 2 ? 3 : maxo == 3 ? 4 : 8;
+    with_type<float, double>(is_f64 ? 1 : 0, [&](auto T) {
+        using real = MH_TYPE(T);
+        with_int<1, 2, 3, 4, 8>(ntap, [&](auto NT) {
+            constexpr int PATH = NT == 1 ? PP_NEAREST : NT == 2 ? PP_LINEAR : PP_GENERIC;
+            if (gather)
+                with_flags([&](auto PULL) {
+                    hipLaunchKernelGGL((pushpull_kernel<real, PATH, NT, PULL>), dim3(nb), dim3(256), 0, s, static_cast<const real*>(source),
+                                       static_cast<const real*>(grid), static_cast<const real*>(target), static_cast<real*>(out), static_cast<real*>(grad), ag);
+                }, pull_only);
+            if (scatter)
+                hipLaunchKernelGGL((pushpull_scatter_kernel<real, PATH, NT>), dim3(nbs), dim3(256), 0, s, static_cast<const real*>(grid),
+                                   static_cast<const real*>(target), static_cast<real*>(out), a, tx, ty, tz);
+        });
+    });
     return launched("pushpull");
 }
 
 // ------------------------------------------------------------------------------------------ post-processing (Activations / AsDiscrete)
 int mh_pointwise_f32(int op, const float* src, float* dst, int64_t n, float param, void* stream) {
     if (!src || !dst || n < 1 || op < 0 || op > PW_ROUND) return fail(MH_ERR_ARG, "pointwise: bad argument");
-    if (n > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "pointwise: problem too large for one launch");
+    if (too_large_for(n)) return fail(MH_ERR_UNSUPPORTED, "pointwise: problem too large for one launch");
     hipLaunchKernelGGL(pointwise_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, op, param);
     return launched("pointwise");
 }
 
 int mh_channel_reduce_f32(int op, const float* src, float* dst, int C, int64_t n, void* stream) {
     if (!src || !dst || C < 1 || n < 1 || (op != CR_ARGMAX && op != CR_SOFTMAX)) return fail(MH_ERR_ARG, "channel_reduce: bad argument");
-    if (n > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "channel_reduce: problem too large for one launch");
+    if (too_large_for(n)) return fail(MH_ERR_UNSUPPORTED, "channel_reduce: problem too large for one launch");
     if (op == CR_ARGMAX) hipLaunchKernelGGL(channel_argmax_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, src, dst, C, (long long)n);
     else hipLaunchKernelGGL(channel_softmax_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, src, dst, C, (long long)n);
     return launched("channel_reduce");
@@ -1543,7 +1449,7 @@ int mh_channel_reduce_f32(int op, const float* src, float* dst, int C, int64_t n
 
 int mh_onehot_f32(const float* labels, float* dst, int K, int64_t n, void* stream) {
     if (!labels || !dst || K < 1 || n < 1) return fail(MH_ERR_ARG, "onehot: bad argument");
-    if (n > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "onehot: problem too large for one launch");
+    if (too_large_for(n)) return fail(MH_ERR_UNSUPPORTED, "onehot: problem too large for one launch");
     hipLaunchKernelGGL(onehot_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, labels, dst, K, (long long)n);
     return launched("onehot");
 }
@@ -1557,10 +1463,7 @@ int mh_scale_intensity_range_f32(const float* src, float* dst, int64_t n, float 
     p.a_min = a_min; p.div = a_div; p.b_scale = b_scale; p.b_min = b_min; p.lo = lo; p.hi = hi;
     p.rescale = rescale != 0; p.clip_lo = clip_lo != 0; p.clip_hi = clip_hi != 0;
     const dim3 grid(blocks_for((n + 3) / 4));
-    if (aligned(src, 16) && aligned(dst, 16))
-        hipLaunchKernelGGL(scale_range_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, p);
-    else
-        hipLaunchKernelGGL(scale_range_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, p);
+    with_flags([&](auto VEC) { hipLaunchKernelGGL(scale_range_kernel<VEC>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, p); }, aligned(src, 16) && aligned(dst, 16));
     return launched("scale_intensity_range");
 }
 
@@ -1573,10 +1476,8 @@ int mh_foreground_bbox_workspace_ints(int D, int H) {
 int mh_foreground_bbox_f32(const float* src, int C, int D, int H, int W, int32_t* workspace, int32_t* box6, void* stream) {
     if (!src || !workspace || !box6 || C < 1 || D < 1 || H < 1 || W < 1) return fail(MH_ERR_ARG, "foreground_bbox: bad argument");
     const int parts = mh_foreground_bbox_workspace_ints(D, H) / 6;
-    if (W % 4 == 0 && aligned(src, 16) && ((long long)D * H * W) % 4 == 0)
-        hipLaunchKernelGGL(bbox_partial_kernel<true>, dim3(parts), dim3(256), 0, (hipStream_t)stream, src, C, D, H, W, workspace);
-    else
-        hipLaunchKernelGGL(bbox_partial_kernel<false>, dim3(parts), dim3(256), 0, (hipStream_t)stream, src, C, D, H, W, workspace);
+    with_flags([&](auto VEC) { hipLaunchKernelGGL(bbox_partial_kernel<VEC>, dim3(parts), dim3(256), 0, (hipStream_t)stream, src, C, D, H, W, workspace); },
+               W % 4 == 0 && aligned(src, 16) && ((long long)D * H * W) % 4 == 0);
     hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, workspace, parts, box6);
     return launched("foreground_bbox");
 }
@@ -1606,10 +1507,7 @@ int mh_normalize_stats_f32(const float* src, int C, int64_t n, int nonzero, doub
     const int parts = normalize_parts(n);
     const bool vec = aligned(src, 16) && n % 4 == 0;
     const dim3 grid((unsigned)parts, (unsigned)C);
-#define MH_NS_LAUNCH(NZ_, V_) hipLaunchKernelGGL((masked_stats_kernel<NZ_, V_>), grid, dim3(256), 0, (hipStream_t)stream, src, (long long)n, workspace)
-    if (nonzero) { if (vec) MH_NS_LAUNCH(true, true); else MH_NS_LAUNCH(true, false); }
-    else { if (vec) MH_NS_LAUNCH(false, true); else MH_NS_LAUNCH(false, false); }
-#undef MH_NS_LAUNCH
+    with_flags([&](auto NZ, auto VEC) { hipLaunchKernelGGL((masked_stats_kernel<NZ, VEC>), grid, dim3(256), 0, (hipStream_t)stream, src, (long long)n, workspace); }, nonzero != 0, vec);
     hipLaunchKernelGGL(masked_stats_finalize_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, workspace, parts, subdiv);
     return launched("normalize_stats");
 }
@@ -1619,10 +1517,7 @@ int mh_normalize_apply_f32(const float* src, float* dst, int C, int64_t n, int n
     if (n > 0x7fffffffLL * 1024) return fail(MH_ERR_UNSUPPORTED, "normalize_apply: problem too large for one launch");
     const bool vec = aligned(src, 16) && aligned(dst, 16) && n % 4 == 0;
     const dim3 grid(blocks_for((n + 3) / 4), (unsigned)C);
-#define MH_NA_LAUNCH(NZ_, V_) hipLaunchKernelGGL((masked_normalize_kernel<NZ_, V_>), grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, subdiv)
-    if (nonzero) { if (vec) MH_NA_LAUNCH(true, true); else MH_NA_LAUNCH(true, false); }
-    else { if (vec) MH_NA_LAUNCH(false, true); else MH_NA_LAUNCH(false, false); }
-#undef MH_NA_LAUNCH
+    with_flags([&](auto NZ, auto VEC) { hipLaunchKernelGGL((masked_normalize_kernel<NZ, VEC>), grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, subdiv); }, nonzero != 0, vec);
     return launched("normalize_apply");
 }
 
@@ -1634,10 +1529,8 @@ int64_t mh_minmax_workspace_floats(int C, int64_t n) {
 int mh_minmax_f32(const float* src, int C, int64_t n, float* workspace, float* table, void* stream) {
     if (!src || !workspace || !table || C < 1 || C > 65535 || n < 1) return fail(MH_ERR_ARG, "minmax: bad argument");
     const int parts = normalize_parts(n);
-    if (aligned(src, 16) && n % 4 == 0)
-        hipLaunchKernelGGL(minmax_partial_kernel<true>, dim3((unsigned)parts, (unsigned)C), dim3(256), 0, (hipStream_t)stream, src, (long long)n, workspace);
-    else
-        hipLaunchKernelGGL(minmax_partial_kernel<false>, dim3((unsigned)parts, (unsigned)C), dim3(256), 0, (hipStream_t)stream, src, (long long)n, workspace);
+    with_flags([&](auto VEC) { hipLaunchKernelGGL(minmax_partial_kernel<VEC>, dim3((unsigned)parts, (unsigned)C), dim3(256), 0, (hipStream_t)stream, src, (long long)n, workspace); },
+               aligned(src, 16) && n % 4 == 0);
     hipLaunchKernelGGL(minmax_final_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, workspace, parts, table);
     return launched("minmax");
 }
@@ -1649,10 +1542,8 @@ int mh_minmax_scale_f32(const float* src, float* dst, int C, int64_t n, const fl
     MinMaxScale p;
     p.b_scale = b_scale; p.b_min = b_min; p.flat_mul = flat_mul; p.rescale = rescale != 0; p.flat_has_mul = flat_has_mul != 0;
     const dim3 grid(blocks_for((n + 3) / 4), (unsigned)C);
-    if (aligned(src, 16) && aligned(dst, 16) && n % 4 == 0)
-        hipLaunchKernelGGL(minmax_scale_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table, p);
-    else
-        hipLaunchKernelGGL(minmax_scale_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table, p);
+    with_flags([&](auto VEC) { hipLaunchKernelGGL(minmax_scale_kernel<VEC>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table, p); },
+               aligned(src, 16) && aligned(dst, 16) && n % 4 == 0);
     return launched("minmax_scale");
 }
 
@@ -1688,14 +1579,11 @@ static int select_launch(const char* what, const float* src, int C, int64_t n, i
     const bool vec = aligned(src, 16) && (C == 1 || n % 4 == 0);
     const dim3 grid((unsigned)select_parts(n), (unsigned)C);
     const size_t per_pass = (size_t)C * SEL_MAX_RANKS * SEL_BINS;
-#define MH_SEL_PASS(P_)                                                                                                                                \
-    if (vec) hipLaunchKernelGGL((select_count_kernel<P_, true>), grid, dim3(256), 0, s, src, (long long)n, hist + (P_) * per_pass, state);            \
-    else hipLaunchKernelGGL((select_count_kernel<P_, false>), grid, dim3(256), 0, s, src, (long long)n, hist + (P_) * per_pass, state);               \
-    hipLaunchKernelGGL(select_scan_kernel<P_>, dim3((unsigned)C), dim3(256), 0, s, (const unsigned*)(hist + (P_) * per_pass), state, rk, os)
-    MH_SEL_PASS(0);
-    MH_SEL_PASS(1);
-    MH_SEL_PASS(2);
-#undef MH_SEL_PASS
+    for (int pass = 0; pass < 3; ++pass)
+        with_int<0, 1, 2>(pass, [&](auto P) {
+            with_flags([&](auto VEC) { hipLaunchKernelGGL((select_count_kernel<P, VEC>), grid, dim3(256), 0, s, src, (long long)n, hist + P * per_pass, state); }, vec);
+            hipLaunchKernelGGL(select_scan_kernel<P>, dim3((unsigned)C), dim3(256), 0, s, (const unsigned*)(hist + P * per_pass), state, rk, os);
+        });
     return MH_OK;
 }
 
@@ -1728,10 +1616,8 @@ int mh_scale_intensity_table_f32(const float* src, float* dst, int C, int64_t n,
     p.b_scale = b_scale; p.b_min = b_min; p.lo = lo; p.hi = hi;
     p.rescale = rescale != 0; p.flat_add = flat_add != 0; p.clip_lo = clip_lo != 0; p.clip_hi = clip_hi != 0;
     const dim3 grid(blocks_for((n + 3) / 4), (unsigned)C);
-    if (aligned(src, 16) && aligned(dst, 16) && n % 4 == 0)
-        hipLaunchKernelGGL(table_scale_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table, p);
-    else
-        hipLaunchKernelGGL(table_scale_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table, p);
+    with_flags([&](auto VEC) { hipLaunchKernelGGL(table_scale_kernel<VEC>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table, p); },
+               aligned(src, 16) && aligned(dst, 16) && n % 4 == 0);
     return launched("scale_intensity_table");
 }
 
@@ -1739,10 +1625,8 @@ int mh_clamp_table_f32(const float* src, float* dst, int C, int64_t n, const flo
     if (!src || !dst || !table || C < 1 || C > 65535 || n < 1) return fail(MH_ERR_ARG, "clamp_table: bad argument");
     if (n > 0x7fffffffLL * 1024) return fail(MH_ERR_UNSUPPORTED, "clamp_table: problem too large for one launch");
     const dim3 grid(blocks_for((n + 3) / 4), (unsigned)C);
-    if (aligned(src, 16) && aligned(dst, 16) && n % 4 == 0)
-        hipLaunchKernelGGL(table_clamp_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table);
-    else
-        hipLaunchKernelGGL(table_clamp_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table);
+    with_flags([&](auto VEC) { hipLaunchKernelGGL(table_clamp_kernel<VEC>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, table); },
+               aligned(src, 16) && aligned(dst, 16) && n % 4 == 0);
     return launched("clamp_table");
 }
 
@@ -1795,6 +1679,17 @@ int64_t mh_overlap_sums_workspace_bytes(int B, int K, int64_t n) {
     return (int64_t)B * overlap_parts_bound(n) * K * OV_SLOTS * (int64_t)sizeof(double);
 }
 
+// (form, dtype) of a side as a code 0 channel f32, 1 channel u8, 2 labels f32, 3 labels u8, 4 labels i64 -> f(form, element type)
+template <class F> static void with_overlap_side(int kind, F&& f) {
+    switch (kind) {
+    case 0: f(int_c<OV_CHANNEL>, type_tag<float>{}); break;
+    case 1: f(int_c<OV_CHANNEL>, type_tag<unsigned char>{}); break;
+    case 2: f(int_c<OV_LABELS>, type_tag<float>{}); break;
+    case 3: f(int_c<OV_LABELS>, type_tag<unsigned char>{}); break;
+    default: f(int_c<OV_LABELS>, type_tag<long long>{}); break;
+    }
+}
+
 template <int PF, typename TP, int YF, typename TY>
 static void overlap_launch(const void* pred, const void* truth, int B, int K, long long n, double* workspace, double* out, hipStream_t stream) {
     constexpr int V = (sizeof(TP) < sizeof(TY) ? 16 / (int)sizeof(TP) : 16 / (int)sizeof(TY));
@@ -1823,26 +1718,10 @@ int mh_overlap_sums(const void* pred, int pred_form, int pred_dtype, const void*
     const hipStream_t st = (hipStream_t)stream;
     const long long nn = (long long)n;
     double* ws = (double*)workspace;
-    typedef unsigned char u8;
-    typedef long long i64;
-    // (form, dtype) of a side -> 0 channel f32, 1 channel u8, 2 labels f32, 3 labels u8, 4 labels i64
     const int sp = pred_form == OV_CHANNEL ? pred_dtype : 2 + pred_dtype, sy = truth_form == OV_CHANNEL ? truth_dtype : 2 + truth_dtype;
-#define MH_OV_TRUTH(PF_, TP_)                                                                          \
-    switch (sy) {                                                                                      \
-    case 0: overlap_launch<PF_, TP_, OV_CHANNEL, float>(pred, truth, B, K, nn, ws, out, st); break;    \
-    case 1: overlap_launch<PF_, TP_, OV_CHANNEL, u8>(pred, truth, B, K, nn, ws, out, st); break;       \
-    case 2: overlap_launch<PF_, TP_, OV_LABELS, float>(pred, truth, B, K, nn, ws, out, st); break;     \
-    case 3: overlap_launch<PF_, TP_, OV_LABELS, u8>(pred, truth, B, K, nn, ws, out, st); break;        \
-    default: overlap_launch<PF_, TP_, OV_LABELS, i64>(pred, truth, B, K, nn, ws, out, st); break;      \
-    }
-    switch (sp) {
-    case 0: MH_OV_TRUTH(OV_CHANNEL, float) break;
-    case 1: MH_OV_TRUTH(OV_CHANNEL, u8) break;
-    case 2: MH_OV_TRUTH(OV_LABELS, float) break;
-    case 3: MH_OV_TRUTH(OV_LABELS, u8) break;
-    default: MH_OV_TRUTH(OV_LABELS, i64) break;
-    }
-#undef MH_OV_TRUTH
+    with_overlap_side(sp, [&](auto PF, auto TP) {
+        with_overlap_side(sy, [&](auto YF, auto TY) { overlap_launch<PF, MH_TYPE(TP), YF, MH_TYPE(TY)>(pred, truth, B, K, nn, ws, out, st); });
+    });
     return launched("overlap_sums");
 }
 
@@ -1857,15 +1736,17 @@ static int surf_side(const char* who, const char* side, int form, int dtype) {
     if (form == OV_LABELS && dtype == ED_BOOL) return fail(MH_ERR_ARG, "%s: a label-map %s is float32, uint8 or int64, not bool", who, side);
     return form == OV_CHANNEL ? (dtype == OV_F32 ? 0 : dtype == OV_U8 ? 1 : 2) : (dtype == OV_F32 ? 3 : dtype == OV_U8 ? 4 : 5);
 }
-#define MH_ED_SIDE(kind, CALL)                                          \
-    switch (kind) {                                                     \
-    case 0: { CALL(OV_CHANNEL, float, false); } break;                  \
-    case 1: { CALL(OV_CHANNEL, unsigned char, false); } break;          \
-    case 2: { CALL(OV_CHANNEL, unsigned char, true); } break;           \
-    case 3: { CALL(OV_LABELS, float, false); } break;                   \
-    case 4: { CALL(OV_LABELS, unsigned char, false); } break;           \
-    default: { CALL(OV_LABELS, long long, false); } break;              \
+// surf_side's code -> f(form, element type, is bool)
+template <class F> static void with_surf_side(int kind, F&& f) {
+    switch (kind) {
+    case 0: f(int_c<OV_CHANNEL>, type_tag<float>{}, std::false_type{}); break;
+    case 1: f(int_c<OV_CHANNEL>, type_tag<unsigned char>{}, std::false_type{}); break;
+    case 2: f(int_c<OV_CHANNEL>, type_tag<unsigned char>{}, std::true_type{}); break;
+    case 3: f(int_c<OV_LABELS>, type_tag<float>{}, std::false_type{}); break;
+    case 4: f(int_c<OV_LABELS>, type_tag<unsigned char>{}, std::false_type{}); break;
+    default: f(int_c<OV_LABELS>, type_tag<long long>{}, std::false_type{}); break;
     }
+}
 
 // rows of a host item table: extents 1 .. 2048 and every box inside [0, total); the largest extents come back for the grids
 static int surf_items_ok(const char* who, const int64_t* items, const void* items_dev, int nitems, int64_t total, int64_t* max_rows, int64_t* max_cols,
@@ -1904,18 +1785,12 @@ int mh_surface_bbox(const void* pred, int pred_form, int pred_dtype, const void*
     if (B > 65535 || nc > 65535) return fail(MH_ERR_UNSUPPORTED, "surface_bbox: problem too large for one launch");
     const hipStream_t st = (hipStream_t)stream;
     const dim3 grid(ED_BOX_BLOCKS, (unsigned)nc, (unsigned)B);
-#define MH_ED_BOX(FORM_, T_, BOOL_) hipLaunchKernelGGL((surf_bbox_partial_kernel<FORM_, T_, BOOL_>), grid, dim3(256), 0, st, (const T_*)src, K, c0, D, H, W, side, (int*)workspace)
-    {
-        const void* src = pred;
-        const int side = 0;
-        MH_ED_SIDE(kp, MH_ED_BOX)
+    for (int side = 0; side < 2; ++side) {
+        const void* src = side ? truth : pred;
+        with_surf_side(side ? kt : kp, [&](auto FORM, auto T, auto BOOL) {
+            hipLaunchKernelGGL((surf_bbox_partial_kernel<FORM, MH_TYPE(T), BOOL>), grid, dim3(256), 0, st, (const MH_TYPE(T)*)src, K, c0, D, H, W, side, (int*)workspace);
+        });
     }
-    {
-        const void* src = truth;
-        const int side = 1;
-        MH_ED_SIDE(kt, MH_ED_BOX)
-    }
-#undef MH_ED_BOX
     hipLaunchKernelGGL(surf_bbox_final_kernel, dim3((unsigned)(B * nc)), dim3(64), 0, st, (const int*)workspace, (int)ED_BOX_BLOCKS, D, H, W, (int*)boxes);
     return launched("surface_bbox");
 }
@@ -1942,9 +1817,9 @@ int mh_mask_edges(const void* src, int form, int dtype, int B, int K, int rank, 
             if (r[9 + a] < 0 || r[9 + a] + r[1 + a] > ext[a]) return fail(MH_ERR_ARG, "mask_edges: the box of item %d leaves the volume", k);
     }
     const dim3 grid(surf_blocks(mv, 4096), (unsigned)nitems);
-#define MH_ED_EDGE(FORM_, T_, BOOL_) hipLaunchKernelGGL((surf_edge_kernel<FORM_, T_, BOOL_>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)src, K, rank, D, H, W, (const EdItem*)items_dev, edges)
-    MH_ED_SIDE(kind, MH_ED_EDGE)
-#undef MH_ED_EDGE
+    with_surf_side(kind, [&](auto FORM, auto T, auto BOOL) {
+        hipLaunchKernelGGL((surf_edge_kernel<FORM, MH_TYPE(T), BOOL>), grid, dim3(256), 0, (hipStream_t)stream, (const MH_TYPE(T)*)src, K, rank, D, H, W, (const EdItem*)items_dev, edges);
+    });
     return launched("mask_edges");
 }
 
@@ -1965,8 +1840,9 @@ static void edt_launch(const void* map, int invert, const EdItem* items, int nit
     hipLaunchKernelGGL((edt_col_kernel<V>), cgrid, dim3(256), 0, st, (const V*)fb, fa, stack, items, 0);
     if (out) {
         const dim3 fgrid(surf_blocks(total, 8192));
-        if (out_dtype == OV_F32) hipLaunchKernelGGL((edt_finish_kernel<V, float>), fgrid, dim3(256), 0, st, (const V*)fa, (long long)total, (float*)out);
-        else hipLaunchKernelGGL((edt_finish_kernel<V, double>), fgrid, dim3(256), 0, st, (const V*)fa, (long long)total, (double*)out);
+        with_type<float, double>(out_dtype == OV_F32 ? 0 : 1, [&](auto O) {
+            hipLaunchKernelGGL((edt_finish_kernel<V, MH_TYPE(O)>), fgrid, dim3(256), 0, st, (const V*)fa, (long long)total, (MH_TYPE(O)*)out);
+        });
     }
 }
 
@@ -1988,13 +1864,9 @@ int mh_edt(const void* map, int map_dtype, int invert, const int64_t* items_host
     if ((mr + 3) / 4 > 0x7fffffffLL) return fail(MH_ERR_UNSUPPORTED, "edt: problem too large for one launch");
     const hipStream_t st = (hipStream_t)stream;
     const EdItem* items = (const EdItem*)items_dev;
-    if (map_dtype == OV_U8) {
-        if (use_spacing) edt_launch<unsigned char, double>(map, invert, items, nitems, total, mr, mc, workspace, out, out_dtype, st);
-        else edt_launch<unsigned char, int>(map, invert, items, nitems, total, mr, mc, workspace, out, out_dtype, st);
-    } else {
-        if (use_spacing) edt_launch<float, double>(map, invert, items, nitems, total, mr, mc, workspace, out, out_dtype, st);
-        else edt_launch<float, int>(map, invert, items, nitems, total, mr, mc, workspace, out, out_dtype, st);
-    }
+    with_type<float, unsigned char>(map_dtype == OV_U8 ? 1 : 0, [&](auto T) {
+        with_type<int, double>(use_spacing ? 1 : 0, [&](auto V) { edt_launch<MH_TYPE(T), MH_TYPE(V)>(map, invert, items, nitems, total, mr, mc, workspace, out, out_dtype, st); });
+    });
     return launched("edt");
 }
 
@@ -2019,8 +1891,9 @@ int mh_surface_records(const uint8_t* edges, const void* field, int use_spacing,
     const dim3 grid(surf_blocks(mv, ED_REC_BLOCKS), (unsigned)nitems);
     const hipStream_t st = (hipStream_t)stream;
     const EdItem* items = (const EdItem*)items_dev;
-    if (use_spacing) hipLaunchKernelGGL(surf_partial_kernel<double>, grid, dim3(256), 0, st, edges, (const double*)field, items, write, (double*)workspace, distances, (long long)ndist);
-    else hipLaunchKernelGGL(surf_partial_kernel<int>, grid, dim3(256), 0, st, edges, (const int*)field, items, write, (double*)workspace, distances, (long long)ndist);
+    with_type<int, double>(use_spacing ? 1 : 0, [&](auto V) {
+        hipLaunchKernelGGL(surf_partial_kernel<MH_TYPE(V)>, grid, dim3(256), 0, st, edges, (const MH_TYPE(V)*)field, items, write, (double*)workspace, distances, (long long)ndist);
+    });
     if (!write) hipLaunchKernelGGL(surf_final_kernel, dim3((unsigned)nitems), dim3(64), 0, st, (const double*)workspace, (int)grid.x, records);
     return launched("surface_records");
 }
@@ -2063,12 +1936,14 @@ static int cc_dtype_ok(const char* who, int dtype) {
     if (dtype != CC_F32 && dtype != CC_U8 && dtype != CC_I64 && dtype != CC_BOOL) return fail(MH_ERR_ARG, "%s: unknown dtype %d", who, dtype);
     return MH_OK;
 }
-#define MH_CC_DTYPE(dtype, CALL)                  \
-    switch (dtype) {                              \
-    case CC_F32: { CALL(float); } break;          \
-    case CC_I64: { CALL(long long); } break;      \
-    default: { CALL(unsigned char); } break;      \
+// a checked dtype code -> f(element type): uint8 and bool share the byte form
+template <class F> static void with_cc_dtype(int dtype, F&& f) {
+    switch (dtype) {
+    case CC_F32: f(type_tag<float>{}); break;
+    case CC_I64: f(type_tag<long long>{}); break;
+    default: f(type_tag<unsigned char>{}); break;
     }
+}
 
 int mh_cc_label(const void* src, int dtype, int64_t src_elems, int rank, int connectivity, const int64_t* items_host, const void* items_dev, int nitems,
                 int64_t total, int32_t* labels, void* stream) {
@@ -2087,12 +1962,11 @@ int mh_cc_label(const void* src, int dtype, int64_t src_elems, int rank, int con
     const CcItem* items = (const CcItem*)items_dev;
     const int64_t rblocks = (mr + 3) / 4;
     const dim3 rgrid((unsigned)(rblocks > 65536 ? 65536 : rblocks), (unsigned)nitems), vgrid(surf_blocks(mv, 8192), (unsigned)nitems);
-#define MH_CC_LABEL(T_)                                                                                                              \
-    hipLaunchKernelGGL((cc_rows_kernel<T_>), rgrid, dim3(256), 0, st, (const T_*)src, items, (int*)labels);                          \
-    if (multi) hipLaunchKernelGGL((cc_unite_kernel<T_, true>), vgrid, dim3(256), 0, st, (const T_*)src, items, connectivity, (int*)labels);   \
-    else hipLaunchKernelGGL((cc_unite_kernel<T_, false>), vgrid, dim3(256), 0, st, (const T_*)src, items, connectivity, (int*)labels)
-    MH_CC_DTYPE(dtype, MH_CC_LABEL)
-#undef MH_CC_LABEL
+    with_cc_dtype(dtype, [&](auto T) {
+        using elem = MH_TYPE(T);
+        hipLaunchKernelGGL((cc_rows_kernel<elem>), rgrid, dim3(256), 0, st, (const elem*)src, items, (int*)labels);
+        with_flags([&](auto MULTI) { hipLaunchKernelGGL((cc_unite_kernel<elem, MULTI>), vgrid, dim3(256), 0, st, (const elem*)src, items, connectivity, (int*)labels); }, multi);
+    });
     hipLaunchKernelGGL(cc_flatten_kernel, vgrid, dim3(256), 0, st, items, (int*)labels);
     return launched("cc_label");
 }
@@ -2120,9 +1994,9 @@ int mh_cc_keep(void* data, int dtype, int64_t data_elems, const int32_t* labels,
     int64_t mr, mv;
     if (cc_items_ok("cc_keep", items_host, items_dev, nitems, total, data_elems, rank, false, &mr, &mv) != MH_OK) return MH_ERR_ARG;
     const dim3 grid(surf_blocks(mv, 8192), (unsigned)nitems);
-#define MH_CC_KEEP(T_) hipLaunchKernelGGL((cc_keep_kernel<T_>), grid, dim3(256), 0, (hipStream_t)stream, (T_*)data, (const int*)labels, (const int*)keep, nkeep, (const CcItem*)items_dev)
-    MH_CC_DTYPE(dtype, MH_CC_KEEP)
-#undef MH_CC_KEEP
+    with_cc_dtype(dtype, [&](auto T) {
+        hipLaunchKernelGGL((cc_keep_kernel<MH_TYPE(T)>), grid, dim3(256), 0, (hipStream_t)stream, (MH_TYPE(T)*)data, (const int*)labels, (const int*)keep, nkeep, (const CcItem*)items_dev);
+    });
     return launched("cc_keep");
 }
 
@@ -2138,9 +2012,9 @@ int mh_cc_fill(void* data, int dtype, int64_t data_elems, const int32_t* labels,
         if (mode != CC_FILL_VALUE && mode != CC_FILL_BINARY) return fail(MH_ERR_ARG, "cc_fill: item %d has the unknown fill mode %lld", k, (long long)mode);
     }
     const dim3 grid(surf_blocks(mv, 8192), (unsigned)nitems);
-#define MH_CC_FILL(T_) hipLaunchKernelGGL((cc_fill_kernel<T_>), grid, dim3(256), 0, (hipStream_t)stream, (T_*)data, (const int*)labels, border, (const CcItem*)items_dev)
-    MH_CC_DTYPE(dtype, MH_CC_FILL)
-#undef MH_CC_FILL
+    with_cc_dtype(dtype, [&](auto T) {
+        hipLaunchKernelGGL((cc_fill_kernel<MH_TYPE(T)>), grid, dim3(256), 0, (hipStream_t)stream, (MH_TYPE(T)*)data, (const int*)labels, border, (const CcItem*)items_dev);
+    });
     return launched("cc_fill");
 }
 
@@ -2154,9 +2028,9 @@ int mh_cc_filter(const void* src, void* dst, int dtype, int64_t n, const double*
     ls.n = nlabels;
     for (int k = 0; k < nlabels; ++k) ls.lab[k] = labels[k];
     const dim3 grid(surf_blocks(n, 8192));
-#define MH_CC_FILTER(T_) hipLaunchKernelGGL((cc_filter_kernel<T_>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)src, (T_*)dst, (long long)n, ls)
-    MH_CC_DTYPE(dtype, MH_CC_FILTER)
-#undef MH_CC_FILTER
+    with_cc_dtype(dtype, [&](auto T) {
+        hipLaunchKernelGGL((cc_filter_kernel<MH_TYPE(T)>), grid, dim3(256), 0, (hipStream_t)stream, (const MH_TYPE(T)*)src, (MH_TYPE(T)*)dst, (long long)n, ls);
+    });
     return launched("cc_filter");
 }
 
@@ -2213,8 +2087,7 @@ int mh_median_filter_f32(const float* src, float* dst, int n, int D, int H, int 
     const dim3 grid((unsigned)(p.tiles_x * p.tiles_y * p.tiles_z), (unsigned)n);
     if (p.path == 1) {
         const int vec = W % 4 == 0 && aligned(dst, 16);
-        if (rz) hipLaunchKernelGGL(median3_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, D, H, W, (int)p.tiles_x, (int)p.tiles_y, vec);
-        else hipLaunchKernelGGL(median3_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, D, H, W, (int)p.tiles_x, (int)p.tiles_y, vec);
+        with_int<0, 1>(rz, [&](auto RZ) { hipLaunchKernelGGL(median3_kernel<RZ>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, D, H, W, (int)p.tiles_x, (int)p.tiles_y, vec); });
     } else {
         MedGeneral g;
         g.D = D; g.H = H; g.W = W; g.rz = rz; g.ry = ry; g.rx = rx; g.la = p.la; g.lb = p.lb; g.tiles_x = (int)p.tiles_x; g.tiles_y = (int)p.tiles_y;
@@ -2274,13 +2147,12 @@ int mh_spline_prefilter_f64(const float* src, double* coef, int NC, int rank, in
     for (int i = 0; i < na; ++i) {
         const int ax = axes[i];
         const long long lines = (long long)NC * a.g.N[ax == 0 ? 1 : 0] * a.g.N[ax == 2 ? 1 : 2];
-        if (lines > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "spline_prefilter: problem too large for one launch");
+        if (too_large_for(lines)) return fail(MH_ERR_UNSUPPORTED, "spline_prefilter: problem too large for one launch");
     }
     for (int i = 0; i < na; ++i) {
         a.axis = axes[i];
         const long long lines = (long long)NC * a.g.N[a.axis == 0 ? 1 : 0] * a.g.N[a.axis == 2 ? 1 : 2];
-        if (i == 0) hipLaunchKernelGGL(spline_prefilter_kernel<true>, dim3(blocks_for(lines)), dim3(256), 0, (hipStream_t)stream, src, coef, a);
-        else hipLaunchKernelGGL(spline_prefilter_kernel<false>, dim3(blocks_for(lines)), dim3(256), 0, (hipStream_t)stream, src, coef, a);
+        with_flags([&](auto FIRST) { hipLaunchKernelGGL(spline_prefilter_kernel<FIRST>, dim3(blocks_for(lines)), dim3(256), 0, (hipStream_t)stream, src, coef, a); }, i == 0);
     }
     return launched("spline_prefilter");
 }
@@ -2288,16 +2160,10 @@ int mh_spline_prefilter_f64(const float* src, double* coef, int NC, int rank, in
 template <bool GRID, typename TG>
 static int spline_launch(const void* vol, const TG* grid, float* dst, const SplineSampleArgs& a, hipStream_t s) {
     const unsigned nb = blocks_for((long long)a.Do * a.Ho * a.Wo);
-#define MH_SP(O_, T_) hipLaunchKernelGGL((spline_resample_kernel<O_, T_, TG, GRID>), dim3(nb), dim3(256), 0, s, static_cast<const T_*>(vol), grid, dst, a)
-    switch (a.order) {
-        case 0: MH_SP(0, float); break;
-        case 1: MH_SP(1, float); break;
-        case 2: MH_SP(2, double); break;
-        case 3: MH_SP(3, double); break;
-        case 4: MH_SP(4, double); break;
-        default: MH_SP(5, double); break;
-    }
-#undef MH_SP
+    with_int<0, 1, 2, 3, 4, 5>(a.order, [&](auto ORDER) {
+        using T = std::conditional_t<(ORDER < 2), float, double>;      // orders 0 and 1 read the image, the others its float64 coefficients
+        hipLaunchKernelGGL((spline_resample_kernel<ORDER, T, TG, GRID>), dim3(nb), dim3(256), 0, s, static_cast<const T*>(vol), grid, dst, a);
+    });
     return launched("spline_resample");
 }
 
@@ -2306,7 +2172,7 @@ static int spline_sample_args(SplineSampleArgs& a, const char* what, const void*
     if (int e = spline_geom(a.g, what, NC, rank, Di, Hi, Wi, order, mode)) return e;
     if (!vol || !dst) return fail(MH_ERR_ARG, "%s: null pointer", what);
     if (Do < 1 || Ho < 1 || Wo < 1) return fail(MH_ERR_ARG, "%s: bad output shape (%d, %d, %d)", what, Do, Ho, Wo);
-    if ((long long)Do * Ho * Wo > 0x7fffffffLL * 256) return fail(MH_ERR_UNSUPPORTED, "%s: problem too large for one launch", what);
+    if (too_large_for((long long)Do * Ho * Wo)) return fail(MH_ERR_UNSUPPORTED, "%s: problem too large for one launch", what);
     a.Do = Do; a.Ho = Ho; a.Wo = Wo; a.order = order; a.mode = mode;
     for (int i = 0; i < 12; ++i) a.m[i] = 0.0;
     for (int i = 0; i < 3; ++i) { a.ga[i] = 1.0; a.gb[i] = 0.0; }
@@ -2395,12 +2261,6 @@ int mh_bilateral_filter_accepts(int C, int D, int H, int W, int K, int is_f64) {
     return bilateral_plan(C, D, H, W, K, is_f64, p, &why);
 }
 
-template <int C>
-static void bilateral_tile_launch(const float* src, float* dst, const BilTile& g, int large, dim3 grid, hipStream_t stream) {
-    if (large) hipLaunchKernelGGL((bilateral_tile_kernel<C, BIL_LDS_LARGE>), grid, dim3(256), 0, stream, src, dst, g);
-    else hipLaunchKernelGGL((bilateral_tile_kernel<C, BIL_LDS_SMALL>), grid, dim3(256), 0, stream, src, dst, g);
-}
-
 template <typename T>
 static int bilateral_filter(const T* src, T* dst, int B, int C, int D, int H, int W, float spatial_sigma, float color_sigma, void* stream) {
     const int is_f64 = sizeof(T) == 8;
@@ -2433,12 +2293,11 @@ static int bilateral_filter(const T* src, T* dst, int B, int C, int D, int H, in
             g.D = D; g.H = H; g.W = W; g.K = K; g.hz = p.hz; g.hy = p.hy; g.hx = p.hx; g.la = p.la; g.lb = p.lb; g.pitch = p.pitch; g.py = p.py; g.pz = p.pz;
             g.tiles_x = (int)p.tiles_x; g.tiles_y = (int)p.tiles_y; g.vec = W % 4 == 0 && aligned(dst, 16);
             g.ks = (float)((double)ks * log2e); g.s = s; g.inv_s = inv_s;
-            switch (C) {
-                case 1: bilateral_tile_launch<1>(src, dst, g, p.lds, grid, (hipStream_t)stream); break;
-                case 2: bilateral_tile_launch<2>(src, dst, g, p.lds, grid, (hipStream_t)stream); break;
-                case 3: bilateral_tile_launch<3>(src, dst, g, p.lds, grid, (hipStream_t)stream); break;
-                default: bilateral_tile_launch<4>(src, dst, g, p.lds, grid, (hipStream_t)stream); break;
-            }
+            with_int<1, 2, 3, 4>(C, [&](auto CH) {
+                with_int<BIL_LDS_SMALL, BIL_LDS_LARGE>(p.lds ? BIL_LDS_LARGE : BIL_LDS_SMALL, [&](auto LDS) {
+                    hipLaunchKernelGGL((bilateral_tile_kernel<CH, LDS>), grid, dim3(256), 0, (hipStream_t)stream, src, dst, g);
+                });
+            });
         }
     } else {
         BilGeneric<T> g;
@@ -2484,79 +2343,54 @@ int mh_separable_filter3d_f32(const float* src, float* dst, int NC, int D, int H
         // up to 9 taps: the DPP / forward-accumulation form (gauss3d_rowdpp_kernel); development builds: MONAI_AMD_GS_IMPL=v keeps the round-2 row-vector kernel
         const bool dpp = rk <= 9 && (long long)D * H * W * 4 < 0x80000000LL && !(impl && impl[0] == 'v');      // (its loads address a channel volume with 31-bit byte offsets)
         const long long vtiles = (long long)cdiv(W, GV_TX) * cdiv(H, GV_TY);
-        static int vslots[4][2][2];
-        const int vi = rk == 3 ? 0 : rk == 5 ? 1 : rk == 9 ? 2 : 3;
-        int& vs = vslots[vi][iso ? 1 : 0][dpp ? 1 : 0];
-        if (vs == 0) {
-#define MH_GV_SLOTS(RK_) vs = iso ? resident_wgs(gauss3d_rowvec_kernel<RK_, true>, 64 * gv_waves(RK_)) : resident_wgs(gauss3d_rowvec_kernel<RK_, false>, 64 * gv_waves(RK_));
-#define MH_GD_SLOTS(RK_) vs = iso ? resident_wgs(gauss3d_rowdpp_kernel<RK_, true>, 1024) : resident_wgs(gauss3d_rowdpp_kernel<RK_, false>, 1024);
-            switch (rk) {
-                case 3: if (dpp) { MH_GD_SLOTS(3) } else { MH_GV_SLOTS(3) } break;
-                case 5: if (dpp) { MH_GD_SLOTS(5) } else { MH_GV_SLOTS(5) } break;
-                case 9: if (dpp) { MH_GD_SLOTS(9) } else { MH_GV_SLOTS(9) } break;
-                default: MH_GV_SLOTS(17) break;
-            }
-#undef MH_GD_SLOTS
-#undef MH_GV_SLOTS
-        }
-        const int vmin = 4 * rk > 16 ? 4 * rk : 16;
-        const int vchunks = stream_chunks(vtiles * NC, D, vs, rk - 1, vmin, "MONAI_AMD_GS_CHUNKS");
-        a.zchunk = cdiv(D, vchunks);
-        a.nchunk = cdiv(D, a.zchunk);
-        a.pair_ok = 1;
-        const long long vwg = vtiles * a.nchunk * NC;
-        if (vwg > 0x7fffffffLL) return fail(MH_ERR_UNSUPPORTED, "separable_filter3d: problem too large for one launch");
-#define MH_GV(RK_)                                                                                                        \
-        if (iso) hipLaunchKernelGGL((gauss3d_rowvec_kernel<RK_, true>), dim3((unsigned)vwg), dim3(64 * gv_waves(RK_)), 0, s, src, dst, a);   \
-        else hipLaunchKernelGGL((gauss3d_rowvec_kernel<RK_, false>), dim3((unsigned)vwg), dim3(64 * gv_waves(RK_)), 0, s, src, dst, a);
-#define MH_GD(RK_)                                                                                                        \
-        if (iso) hipLaunchKernelGGL((gauss3d_rowdpp_kernel<RK_, true>), dim3((unsigned)vwg), dim3(1024), 0, s, src, dst, a);   \
-        else hipLaunchKernelGGL((gauss3d_rowdpp_kernel<RK_, false>), dim3((unsigned)vwg), dim3(1024), 0, s, src, dst, a);
-        switch (rk) {
-            case 3: if (dpp) { MH_GD(3) } else { MH_GV(3) } break;
-            case 5: if (dpp) { MH_GD(5) } else { MH_GV(5) } break;
-            case 9: if (dpp) { MH_GD(9) } else { MH_GV(9) } break;
-            default: MH_GV(17) break;
-        }
-#undef MH_GD
-#undef MH_GV
+        // `kernel` is the instantiation chosen below, `vs` its own cache of resident workgroups: the occupancy query and the launch share the one pointer
+        auto run = [&](auto kernel, int nt, int& vs) -> int {
+            if (vs == 0) vs = resident_wgs(kernel, nt);
+            const int vmin = 4 * rk > 16 ? 4 * rk : 16;
+            const int vchunks = stream_chunks(vtiles * NC, D, vs, rk - 1, vmin, "MONAI_AMD_GS_CHUNKS");
+            a.zchunk = cdiv(D, vchunks);
+            a.nchunk = cdiv(D, a.zchunk);
+            a.pair_ok = 1;
+            const long long vwg = vtiles * a.nchunk * NC;
+            if (vwg > 0x7fffffffLL) return fail(MH_ERR_UNSUPPORTED, "separable_filter3d: problem too large for one launch");
+            hipLaunchKernelGGL(kernel, dim3((unsigned)vwg), dim3(nt), 0, s, src, dst, a);
+            return MH_OK;
+        };
+        int rc = MH_OK;
+        with_int<3, 5, 9, 17>(rk, [&](auto RK) {
+            with_flags([&](auto ISO) {
+                static int vslots[2];      // [dpp]
+                if constexpr (RK <= 9) {   // the DPP form exists for 3, 5 and 9 taps
+                    if (dpp) { rc = run(gauss3d_rowdpp_kernel<RK, ISO>, 1024, vslots[1]); return; }
+                }
+                rc = run(gauss3d_rowvec_kernel<RK, ISO>, 64 * gv_waves(RK), vslots[0]);
+            }, iso);
+        });
+        if (rc) return rc;
         return launched("separable_filter3d_rowvec");
     }
     // cut z into chunks (each re-filters rk-1 halo planes) that fill whole rounds of the resident workgroup slots
     const long long tiles = (long long)cdiv(W, GS_TX) * cdiv(H, GS_TY);
     const int min_chunk = 4 * rk > 16 ? 4 * rk : 16;
-    static int slots[5][2];
-    const int ri = rk == 3 ? 0 : rk == 5 ? 1 : rk == 9 ? 2 : rk == 17 ? 3 : 4;
-    int& sl = slots[ri][iso ? 1 : 0];
-    if (sl == 0) {
-#define MH_GAUSS_SLOTS(RK_) sl = iso ? resident_wgs(gauss3d_stream_kernel<RK_, true>, 256) : resident_wgs(gauss3d_stream_kernel<RK_, false>, 256);
-        switch (rk) {
-            case 3: MH_GAUSS_SLOTS(3) break;
-            case 5: MH_GAUSS_SLOTS(5) break;
-            case 9: MH_GAUSS_SLOTS(9) break;
-            case 17: MH_GAUSS_SLOTS(17) break;
-            default: MH_GAUSS_SLOTS(33) break;
-        }
-#undef MH_GAUSS_SLOTS
-    }
-    const int nchunk = stream_chunks(tiles * NC, D, sl, rk - 1, min_chunk, "MONAI_AMD_GS_CHUNKS");
-    a.zchunk = cdiv(D, nchunk);
-    a.pair_ok = (W % 2 == 0 && aligned(dst, 8)) ? 1 : 0;
-    a.nchunk = cdiv(D, a.zchunk);
-    const long long nwg = tiles * a.nchunk * NC;
-    if (nwg > 0x7fffffffLL) return fail(MH_ERR_UNSUPPORTED, "separable_filter3d: problem too large for one launch");
-    const dim3 grid((unsigned)nwg);
-#define MH_GAUSS(RK_)                                                                                             \
-    if (iso) hipLaunchKernelGGL((gauss3d_stream_kernel<RK_, true>), grid, dim3(256), 0, s, src, dst, a);          \
-    else hipLaunchKernelGGL((gauss3d_stream_kernel<RK_, false>), grid, dim3(256), 0, s, src, dst, a);
-    switch (rk) {
-        case 3: MH_GAUSS(3) break;
-        case 5: MH_GAUSS(5) break;
-        case 9: MH_GAUSS(9) break;
-        case 17: MH_GAUSS(17) break;
-        default: MH_GAUSS(33) break;
-    }
-#undef MH_GAUSS
+    auto run = [&](auto kernel, int& sl) -> int {       // the occupancy query and the launch share the one pointer; `sl` is this instantiation's cache
+        if (sl == 0) sl = resident_wgs(kernel, 256);
+        const int nchunk = stream_chunks(tiles * NC, D, sl, rk - 1, min_chunk, "MONAI_AMD_GS_CHUNKS");
+        a.zchunk = cdiv(D, nchunk);
+        a.pair_ok = (W % 2 == 0 && aligned(dst, 8)) ? 1 : 0;
+        a.nchunk = cdiv(D, a.zchunk);
+        const long long nwg = tiles * a.nchunk * NC;
+        if (nwg > 0x7fffffffLL) return fail(MH_ERR_UNSUPPORTED, "separable_filter3d: problem too large for one launch");
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(256), 0, s, src, dst, a);
+        return MH_OK;
+    };
+    int rc = MH_OK;
+    with_int<3, 5, 9, 17, 33>(rk, [&](auto RK) {
+        with_flags([&](auto ISO) {
+            static int sl = 0;
+            rc = run(gauss3d_stream_kernel<RK, ISO>, sl);
+        }, iso);
+    });
+    if (rc) return rc;
     return launched("separable_filter3d");
 }
 
@@ -2574,8 +2408,7 @@ int mh_add_act_f32(const mh_tensor5* a_, const mh_tensor5* b_, float slope, cons
     const bool v4 = DHW % 4 == 0 && aligned(a.data, 16) && (!b.data || aligned(b.data, 16)) && aligned(out.data, 16) && a.n_stride % 4 == 0 &&
                     b.n_stride % 4 == 0 && out.n_stride % 4 == 0;
     const dim3 grid((blocks_for(v4 ? DHW / 4 : DHW) + ADD_ACT_CHUNKS - 1) / ADD_ACT_CHUNKS, (unsigned)a.C, (unsigned)a.N);
-    if (v4) hipLaunchKernelGGL((add_act_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, a, b, slope, out);
-    else hipLaunchKernelGGL((add_act_kernel<1>), grid, dim3(256), 0, (hipStream_t)stream, a, b, slope, out);
+    with_int<1, 4>(v4 ? 4 : 1, [&](auto VEC) { hipLaunchKernelGGL((add_act_kernel<VEC>), grid, dim3(256), 0, (hipStream_t)stream, a, b, slope, out); });
     return launched("add_act");
 }
 
@@ -2591,9 +2424,7 @@ int mh_conv1x1_sum2_f32(const mh_tensor5* a_, const mh_tensor5* b_, float slope,
         out.n_stride % 4)
         return fail(MH_ERR_UNSUPPORTED, "conv1x1_sum2: needs 1 .. 8 output channels, D*H*W %% 4 == 0 and 16-byte aligned tensors (got %d channels)", out.C);
     const dim3 grid(blocks_for(DHW / 4), (unsigned)a.N);
-#define MH_1S_CASE(CO) case CO: hipLaunchKernelGGL((conv1x1_sum2_kernel<CO>), grid, dim3(256), 0, (hipStream_t)stream, a, b, slope, w, bias, out); break;
-    switch (out.C) { MH_1S_CASE(1) MH_1S_CASE(2) MH_1S_CASE(3) MH_1S_CASE(4) MH_1S_CASE(5) MH_1S_CASE(6) MH_1S_CASE(7) MH_1S_CASE(8) }
-#undef MH_1S_CASE
+    with_int<1, 2, 3, 4, 5, 6, 7, 8>(out.C, [&](auto CO) { hipLaunchKernelGGL((conv1x1_sum2_kernel<CO>), grid, dim3(256), 0, (hipStream_t)stream, a, b, slope, w, bias, out); });
     return launched("conv1x1_sum2");
 }
 
@@ -2619,13 +2450,9 @@ int mh_pixelshuffle_f32(const mh_tensor5* in_, const mh_tensor5* out_, int fz, i
     if (out.C > 65535 || out.N > 65535) return fail(MH_ERR_UNSUPPORTED, "pixelshuffle: more than 65535 channels / samples in one launch");
     const dim3 grid(blocks_for((long long)out.D * out.H * out.W), (unsigned)out.C, (unsigned)out.N);
     hipStream_t s = (hipStream_t)stream;
-    if (fz == 2) {
-        if (pad_pool) hipLaunchKernelGGL((pixelshuffle_kernel<2, true>), grid, dim3(256), 0, s, in, out);
-        else hipLaunchKernelGGL((pixelshuffle_kernel<2, false>), grid, dim3(256), 0, s, in, out);
-    } else {
-        if (pad_pool) hipLaunchKernelGGL((pixelshuffle_kernel<1, true>), grid, dim3(256), 0, s, in, out);
-        else hipLaunchKernelGGL((pixelshuffle_kernel<1, false>), grid, dim3(256), 0, s, in, out);
-    }
+    with_int<1, 2>(fz, [&](auto FZ) {
+        with_flags([&](auto PADPOOL) { hipLaunchKernelGGL((pixelshuffle_kernel<FZ, PADPOOL>), grid, dim3(256), 0, s, in, out); }, pad_pool != 0);
+    });
     return launched("pixelshuffle");
 }
 
@@ -2635,13 +2462,9 @@ int mh_attention_f32(const float* qkv, float* out, int B, int S, int heads, int 
     if (B > 65535 || heads > 65535) return fail(MH_ERR_UNSUPPORTED, "attention: more than 65535 batches / heads in one launch");
     const dim3 grid((unsigned)cdiv(S, 128), (unsigned)heads, (unsigned)B);
     hipStream_t s = (hipStream_t)stream;
-    switch (head_dim) {          // any sequence length: keys / values stream through LDS (kernels/attention.h)
-        case 32: hipLaunchKernelGGL((attention_h2_kernel<32>), grid, dim3(256), 0, s, qkv, out, S, heads, scale); break;
-        case 64: hipLaunchKernelGGL((attention_h2_kernel<64>), grid, dim3(256), 0, s, qkv, out, S, heads, scale); break;
-        case 96: hipLaunchKernelGGL((attention_h2_kernel<96>), grid, dim3(256), 0, s, qkv, out, S, heads, scale); break;
-        case 128: hipLaunchKernelGGL((attention_h2_kernel<128>), grid, dim3(256), 0, s, qkv, out, S, heads, scale); break;
-        default: return fail(MH_ERR_UNSUPPORTED, "attention: head_dim %d is not built (32, 64, 96, 128 are)", head_dim);
-    }
+    // any sequence length: keys / values stream through LDS (kernels/attention.h)
+    if (!with_int<32, 64, 96, 128>(head_dim, [&](auto HD) { hipLaunchKernelGGL((attention_h2_kernel<HD>), grid, dim3(256), 0, s, qkv, out, S, heads, scale); }))
+        return fail(MH_ERR_UNSUPPORTED, "attention: head_dim %d is not built (32, 64, 96, 128 are)", head_dim);
     return launched("attention");
 }
 
@@ -2656,20 +2479,15 @@ int mh_window_attention_f32(const float* qkv, const float* bias_t, const float* 
     // (|x| < 65504, no input scaling: ADVICE r4), which hidden states behind a LayerNorm satisfy and a caller who asked for exact fp32 did not sign up for
     if ((head_dim == 16 || head_dim == 32) && !(exact_fp32 && S <= WA_MAX_TOKENS)) {
         const dim3 g2((unsigned)cdiv(S, 128), (unsigned)heads, (unsigned)BW);
-        if (head_dim == 16) hipLaunchKernelGGL((window_attention_h2_kernel<16, false>), g2, dim3(256), 0, s0, qkv, bias_t, mask, out, S, heads, nW, scale, WinRel{});
-        else hipLaunchKernelGGL((window_attention_h2_kernel<32, false>), g2, dim3(256), 0, s0, qkv, bias_t, mask, out, S, heads, nW, scale, WinRel{});
+        with_int<16, 32>(head_dim, [&](auto HD) { hipLaunchKernelGGL((window_attention_h2_kernel<HD, false>), g2, dim3(256), 0, s0, qkv, bias_t, mask, out, S, heads, nW, scale, WinRel{}); });
         return launched("window_attention_h2");
     }
     if (S > WA_MAX_TOKENS) return fail(MH_ERR_UNSUPPORTED, "window_attention: %d tokens per window exceed the LDS-resident limit of %d", S, WA_MAX_TOKENS);
     const size_t lds = 0;
     const dim3 grid((unsigned)heads, (unsigned)BW);
     hipStream_t s = (hipStream_t)stream;
-    switch (head_dim) {
-        case 8: hipLaunchKernelGGL((window_attention_kernel<8>), grid, dim3(256), lds, s, qkv, bias_t, mask, out, S, heads, nW, scale); break;
-        case 16: hipLaunchKernelGGL((window_attention_kernel<16>), grid, dim3(256), lds, s, qkv, bias_t, mask, out, S, heads, nW, scale); break;
-        case 32: hipLaunchKernelGGL((window_attention_kernel<32>), grid, dim3(256), lds, s, qkv, bias_t, mask, out, S, heads, nW, scale); break;
-        default: return fail(MH_ERR_UNSUPPORTED, "window_attention: head_dim %d is not built (8, 16, 32 are)", head_dim);
-    }
+    if (!with_int<8, 16, 32>(head_dim, [&](auto HD) { hipLaunchKernelGGL((window_attention_kernel<HD>), grid, dim3(256), lds, s, qkv, bias_t, mask, out, S, heads, nW, scale); }))
+        return fail(MH_ERR_UNSUPPORTED, "window_attention: head_dim %d is not built (8, 16, 32 are)", head_dim);
     return launched("window_attention");
 }
 
@@ -2687,10 +2505,9 @@ int mh_window_attention_rel_f32(const float* qkv, const float* rel_table, int ta
                     table_rows, WA_REL_TOKENS, WA_REL_ROWS);
     const dim3 g2((unsigned)cdiv(S, 128), (unsigned)heads, (unsigned)BW);
     const WinRel rel{rel_table, coord, region, table_rows, coord_off};
-    if (head_dim == 16)
-        hipLaunchKernelGGL((window_attention_h2_kernel<16, true>), g2, dim3(256), 0, (hipStream_t)stream, qkv, (const float*)nullptr, (const float*)nullptr, out, S, heads, nW, scale, rel);
-    else
-        hipLaunchKernelGGL((window_attention_h2_kernel<32, true>), g2, dim3(256), 0, (hipStream_t)stream, qkv, (const float*)nullptr, (const float*)nullptr, out, S, heads, nW, scale, rel);
+    with_int<16, 32>(head_dim, [&](auto HD) {
+        hipLaunchKernelGGL((window_attention_h2_kernel<HD, true>), g2, dim3(256), 0, (hipStream_t)stream, qkv, (const float*)nullptr, (const float*)nullptr, out, S, heads, nW, scale, rel);
+    });
     return launched("window_attention_rel");
 }
 
@@ -2749,21 +2566,15 @@ static int linear_impl(const float* x, const float* packed_w, const float* bias,
     const long long big1 = (long long)((M + DN_BM - 1) / DN_BM) * ntn2;
     if (tile == 128 || (tile == 0 && big1 >= 512)) {
         const dim3 bgrid((unsigned)big1);
-#define MH_LINEAR_BIG(A_, R_) hipLaunchKernelGGL((linear_h2_big_kernel<A_, R_, 1>), bgrid, dim3(512), 0, s, x, wq, tail, bias, residual, y, (int)M, N, K, ntn2, ntn, rowmap)
-        if (act == 1 && residual) MH_LINEAR_BIG(1, true);
-        else if (act == 1) MH_LINEAR_BIG(1, false);
-        else if (residual) MH_LINEAR_BIG(0, true);
-        else MH_LINEAR_BIG(0, false);
-#undef MH_LINEAR_BIG
+        with_int<0, 1>(act, [&](auto ACT) {
+            with_flags([&](auto RES) { hipLaunchKernelGGL((linear_h2_big_kernel<ACT, RES, 1>), bgrid, dim3(512), 0, s, x, wq, tail, bias, residual, y, (int)M, N, K, ntn2, ntn, rowmap); }, residual != nullptr);
+        });
         return launched("linear");
     }
     const dim3 grid((unsigned)total);
-#define MH_LINEAR_LAUNCH(A_, R_) hipLaunchKernelGGL((linear_h2_kernel<A_, R_>), grid, dim3(256), 0, s, x, wq, tail, bias, residual, y, (int)M, N, K, ntn, rowmap)
-    if (act == 1 && residual) MH_LINEAR_LAUNCH(1, true);
-    else if (act == 1) MH_LINEAR_LAUNCH(1, false);
-    else if (residual) MH_LINEAR_LAUNCH(0, true);
-    else MH_LINEAR_LAUNCH(0, false);
-#undef MH_LINEAR_LAUNCH
+    with_int<0, 1>(act, [&](auto ACT) {
+        with_flags([&](auto RES) { hipLaunchKernelGGL((linear_h2_kernel<ACT, RES>), grid, dim3(256), 0, s, x, wq, tail, bias, residual, y, (int)M, N, K, ntn, rowmap); }, residual != nullptr);
+    });
     return launched("linear");
 }
 
@@ -2773,16 +2584,13 @@ static bool layernorm_vec_ok(const float* x, const float* gamma, const float* be
 
 // 16 / 32 / 64 lanes per row, 16-byte vectors (kernels/dense.h); M = output rows
 static void layernorm_vec_launch(const float* x, const float* gamma, const float* beta, float eps, float* y, int64_t M, int K, const int32_t* src_row, hipStream_t s) {
-#define MH_LNV_LAUNCH(G_, NV_)                                                                                                                       \
-    hipLaunchKernelGGL((layernorm_vec_kernel<G_, NV_>), dim3((unsigned)((M + 4 * (64 / G_) - 1) / (4 * (64 / G_)))), dim3(256), 0, s, x, gamma, beta, eps, y, (int)M, K, \
-                       reinterpret_cast<const int*>(src_row))
-    if (K <= 64) MH_LNV_LAUNCH(16, 1);
-    else if (K <= 128) MH_LNV_LAUNCH(32, 1);
-    else if (K <= 256) MH_LNV_LAUNCH(64, 1);
-    else if (K <= 512) MH_LNV_LAUNCH(64, 2);
-    else if (K <= 768) MH_LNV_LAUNCH(64, 3);
-    else MH_LNV_LAUNCH(64, 4);
-#undef MH_LNV_LAUNCH
+    // the row's capacity in 16-byte vectors, G lanes x NV vectors each: 16 x 1, 32 x 1, 64 x 1, 64 x 2, 64 x 3, 64 x 4
+    const int cap = K <= 64 ? 16 : K <= 128 ? 32 : K <= 256 ? 64 : K <= 512 ? 128 : K <= 768 ? 192 : 256;
+    with_int<16, 32, 64, 128, 192, 256>(cap, [&](auto CAP) {
+        constexpr int G = CAP < 64 ? CAP : 64, NV = CAP / G;
+        hipLaunchKernelGGL((layernorm_vec_kernel<G, NV>), dim3((unsigned)((M + 4 * (64 / G) - 1) / (4 * (64 / G)))), dim3(256), 0, s, x, gamma, beta, eps, y, (int)M, K,
+                           reinterpret_cast<const int*>(src_row));
+    });
 }
 
 int mh_layernorm_f32(const float* x, const float* gamma, const float* beta, float eps, float* y, int64_t M, int K, void* stream) {
@@ -2795,14 +2603,8 @@ int mh_layernorm_f32(const float* x, const float* gamma, const float* beta, floa
         return launched("layernorm");
     }
     const dim3 grid((unsigned)((M + 3) / 4));
-#define MH_LN_LAUNCH(NV_) hipLaunchKernelGGL((layernorm_kernel<NV_>), grid, dim3(256), 0, s, x, gamma, beta, eps, y, (int)M, K)
-    if (K <= 64) MH_LN_LAUNCH(1);
-    else if (K <= 128) MH_LN_LAUNCH(2);
-    else if (K <= 256) MH_LN_LAUNCH(4);
-    else if (K <= 512) MH_LN_LAUNCH(8);
-    else if (K <= 1024) MH_LN_LAUNCH(16);
-    else MH_LN_LAUNCH(64);
-#undef MH_LN_LAUNCH
+    const int nv = K <= 64 ? 1 : K <= 128 ? 2 : K <= 256 ? 4 : K <= 512 ? 8 : K <= 1024 ? 16 : 64;      // values per lane
+    with_int<1, 2, 4, 8, 16, 64>(nv, [&](auto NV) { hipLaunchKernelGGL((layernorm_kernel<NV>), grid, dim3(256), 0, s, x, gamma, beta, eps, y, (int)M, K); });
     return launched("layernorm");
 }
 
@@ -2832,21 +2634,14 @@ int mh_conv3d_k3_strided3_f32(const mh_tensor5* in_, const float* packed_w, cons
     hipStream_t s = (hipStream_t)stream;
     const unsigned nbv = blocks_for((long long)out.D * out.H * out.W);
     if (out.C <= 8) {      // few output channels (e.g. UNet's 5-class top level): one exact-width pass, no channel guards
-#define MH_STRIDED_CASE(C_)                                                                                                     \
-    case C_:                                                                                                                    \
-        hipLaunchKernelGGL((conv3d_k3_strided_kernel<C_, true>), dim3(nbv, 1u, (unsigned)out.N), dim3(256), 0, s, in, packed_w, bias, out, sz, sy, sx); \
-        break;
-        switch (out.C) {
-            MH_STRIDED_CASE(1) MH_STRIDED_CASE(2) MH_STRIDED_CASE(3) MH_STRIDED_CASE(4)
-            MH_STRIDED_CASE(5) MH_STRIDED_CASE(6) MH_STRIDED_CASE(7) MH_STRIDED_CASE(8)
-        }
-#undef MH_STRIDED_CASE
+        with_int<1, 2, 3, 4, 5, 6, 7, 8>(out.C, [&](auto CO) {
+            hipLaunchKernelGGL((conv3d_k3_strided_kernel<CO, true>), dim3(nbv, 1u, (unsigned)out.N), dim3(256), 0, s, in, packed_w, bias, out, sz, sy, sx);
+        });
         return launched("conv3d_k3_strided");
     }
     constexpr int COT = 16;
     const dim3 grid(nbv, (unsigned)cdiv(out.C, COT), (unsigned)out.N);
-    if (out.C % COT == 0) hipLaunchKernelGGL((conv3d_k3_strided_kernel<COT, true>), grid, dim3(256), 0, s, in, packed_w, bias, out, sz, sy, sx);
-    else hipLaunchKernelGGL((conv3d_k3_strided_kernel<COT, false>), grid, dim3(256), 0, s, in, packed_w, bias, out, sz, sy, sx);
+    with_flags([&](auto FULL) { hipLaunchKernelGGL((conv3d_k3_strided_kernel<COT, FULL>), grid, dim3(256), 0, s, in, packed_w, bias, out, sz, sy, sx); }, out.C % COT == 0);
     return launched("conv3d_k3_strided");
 }
 
@@ -2869,10 +2664,13 @@ int mh_deconv_k3_f32(const mh_tensor5* in_, const float* w, const float* bias, c
     if (stride == 2 && aligned(out.data, 8) && out.n_stride % 2 == 0) {
         const unsigned nb = blocks_for((long long)in.D * in.H * in.W);
         hipStream_t s = (hipStream_t)stream;
-        if (out.C % 8 == 0) hipLaunchKernelGGL((deconv_k3s2_kernel<8, true>), dim3(nb, (unsigned)(out.C / 8), (unsigned)out.N), dim3(256), 0, s, in, w, bias, out);
-        else if (out.C == 5) hipLaunchKernelGGL((deconv_k3s2_kernel<5, true>), dim3(nb, 1u, (unsigned)out.N), dim3(256), 0, s, in, w, bias, out);
-        else if (out.C <= 4) hipLaunchKernelGGL((deconv_k3s2_kernel<4, false>), dim3(nb, 1u, (unsigned)out.N), dim3(256), 0, s, in, w, bias, out);
-        else hipLaunchKernelGGL((deconv_k3s2_kernel<8, false>), dim3(nb, (unsigned)cdiv(out.C, 8), (unsigned)out.N), dim3(256), 0, s, in, w, bias, out);
+        auto launch = [&](auto COT, auto FULL) {      // four forms exist: whole groups of 8, exactly 5, up to 4, partial groups of 8
+            hipLaunchKernelGGL((deconv_k3s2_kernel<COT, FULL>), dim3(nb, (unsigned)cdiv(out.C, COT), (unsigned)out.N), dim3(256), 0, s, in, w, bias, out);
+        };
+        if (out.C % 8 == 0) launch(int_c<8>, std::true_type{});
+        else if (out.C == 5) launch(int_c<5>, std::true_type{});
+        else if (out.C <= 4) launch(int_c<4>, std::false_type{});
+        else launch(int_c<8>, std::false_type{});
         return launched("deconv_k3s2");
     }
     constexpr int COT = 16;
